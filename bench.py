@@ -7,12 +7,25 @@ random-init weights. ``value`` is the WHOLE-JOB aggregate across all ranks.
 
 Run directly (single GPU) or under torchrun for N>1:
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs bench_out/
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
         --master-addr 127.0.0.1 bench.py --gpus 8 --steps 10 --warmup 3
 
 Each timed step is a full training iteration: frozen-VAE image encode,
 transformer forward, loss, backward, bucketed RCCL gradient all-reduce,
 grad clip, Adam step — nothing cached, nothing skipped.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON
+result line; that is all the headline figure needs, so it is all a plain
+run does. ``--full`` is where any additional measurement or check belongs
+(other configs, baselines, per-kernel figures); none exists today, so
+``--full`` currently runs exactly the plain benchmark.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its
+caller as ``DIR/<name>.npy`` (float32): the scalar ``loss`` for
+``--mode train``, the decoded ``images`` for ``--mode generate``. Model
+weights and the data pool are seeded, so two runs with the same arguments
+see identical inputs and two builds can be compared output for output.
 """
 
 import argparse
@@ -22,6 +35,9 @@ import sys
 import time
 
 import torch
+
+# --dump-outputs budget: 64 MB in all, as float32 elements
+DUMP_MAX_ELEMS = (64 << 20) // 4
 
 CONFIGS = {
     # BASELINE.json configs B-D (training). Default: the headline C shape.
@@ -63,7 +79,21 @@ def parse_args():
                    help='e4m3 forward path for the projection GEMMs')
     p.add_argument('--eager', action='store_true',
                    help='force eager ops on GPU (baseline comparison)')
-    return p.parse_args()
+    p.add_argument('--full', action='store_true',
+                   help='also run every additional measurement/check beyond '
+                        'the headline figure (none today: same as a plain '
+                        'run)')
+    p.add_argument('--dump-outputs', dest='dump_outputs', type=str,
+                   default=None, metavar='DIR',
+                   help='after the timed steps, write what the last timed '
+                        'step returned as DIR/<name>.npy (float32, <= 64 MB '
+                        'in all)')
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be >= 1')
+    if args.warmup < 0:
+        p.error('--warmup must be >= 0')
+    return args
 
 
 def maybe_self_launch(args):
@@ -96,6 +126,23 @@ def build_model(cfg, device):
         attn_types=cfg['attn_types'], reversible=cfg['reversible'],
         shift_tokens=True, rotary_emb=True)
     return dalle.to(device)
+
+
+def dump_outputs(out_dir, outputs):
+    """Write ``{name: tensor}`` as ``out_dir/<name>.npy`` in float32. The
+    64 MB budget is split evenly over the arrays; one that exceeds its share
+    is reduced to a fixed, seeded sample of its flattened elements (same
+    indices every run, in ascending order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_ELEMS // max(len(outputs), 1)
+    for name, t in outputs.items():
+        t = t.detach().to(device='cpu', dtype=torch.float32).contiguous()
+        if t.numel() > share:
+            g = torch.Generator().manual_seed(20240229)
+            idx = torch.randperm(t.numel(), generator=g)[:share].sort().values
+            t = t.flatten()[idx]
+        np.save(os.path.join(out_dir, f'{name}.npy'), t.numpy())
 
 
 def main():
@@ -179,11 +226,11 @@ def main():
     def gen_step(_):
         text = pool[0][0][:1].repeat(args.gen_batch, 1)
         if decoder is not None:
-            decoder.generate(text, filter_thres=0.9,
-                             cond_scale=args.gen_cond_scale)
-        else:
-            with autocast:
-                dalle.generate_images(text, use_cache=True, filter_thres=0.9)
+            return decoder.generate(text, filter_thres=0.9,
+                                    cond_scale=args.gen_cond_scale)
+        with autocast:
+            return dalle.generate_images(text, use_cache=True,
+                                         filter_thres=0.9)
 
     step = train_step if args.mode == 'train' else gen_step
 
@@ -194,8 +241,9 @@ def main():
     if use_cuda:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        step(args.warmup + i)
+        last = step(args.warmup + i)
     if use_cuda:
         torch.cuda.synchronize()
     barrier()
@@ -207,6 +255,10 @@ def main():
         import torch.distributed as dist
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        name = 'loss' if args.mode == 'train' else 'images'
+        dump_outputs(args.dump_outputs, {name: last})
 
     max_mem_gb = round(torch.cuda.max_memory_allocated() / 2**30, 2) \
         if use_cuda else None

@@ -16,6 +16,7 @@ exposes ``--fp8``). Default OFF: the headline BASELINE numbers are bf16.
 """
 
 import os
+import weakref
 
 import torch
 import torch.nn.functional as F
@@ -41,6 +42,17 @@ _w_cache = {}
 _generation = 0
 
 
+def _owner(w):
+    """The tensor that owns ``w``'s storage for cache purposes: the base
+    parameter for a view (fresh slices of one parameter share it), else
+    ``w`` itself. The per-step caches below key on (data_ptr, shape); each
+    entry also holds a weak reference to this owner, so an entry left by a
+    freed parameter is never served to a new one that the allocator placed
+    at the same address with the same shape and version."""
+    base = w._base
+    return base if base is not None else w
+
+
 def fp8_mark_step():
     """Invalidate the per-step weight-quant cache. Call after optimizer
     steps — parameter version counters are not reliably bumped by every
@@ -63,13 +75,14 @@ def _quant_weight(w, ext):
     key = (w.data_ptr(), tuple(w.shape))
     hit = _w_cache.get(key)
     stamp = (w._version, _generation)
-    if hit is not None and hit[0] == stamp:
+    owner = _owner(w)
+    if hit is not None and hit[0] == stamp and hit[3]() is owner:
         return hit[1], hit[2]
     wb = w.detach()
     if wb.dtype != torch.bfloat16:
         wb = wb.to(torch.bfloat16)
     wq, ws = _quant(wb, ext)
-    _w_cache[key] = (stamp, wq, ws)
+    _w_cache[key] = (stamp, wq, ws, weakref.ref(owner))
     return wq, ws
 
 
@@ -85,12 +98,13 @@ def _cached_bf16(w):
     key = (w.data_ptr(), tuple(w.shape))
     stamp = (w._version, _generation)
     hit = _cast_cache.get(key)
-    if hit is not None and hit[0] == stamp:
+    owner = _owner(w)
+    if hit is not None and hit[0] == stamp and hit[2]() is owner:
         return hit[1]
     wb = w.detach().to(torch.bfloat16)
     if len(_cast_cache) > 512:
         _cast_cache.clear()
-    _cast_cache[key] = (stamp, wb)
+    _cast_cache[key] = (stamp, wb, weakref.ref(owner))
     return wb
 
 
@@ -102,7 +116,8 @@ def _transposed_weight(w):
     key = (w.data_ptr(), tuple(w.shape))
     stamp = (w._version, _generation)
     hit = _wt_cache.get(key)
-    if hit is not None and hit[0] == stamp:
+    owner = _owner(w)
+    if hit is not None and hit[0] == stamp and hit[2]() is owner:
         return hit[1]
     wt = w.detach()
     if wt.dtype != torch.bfloat16:
@@ -110,7 +125,7 @@ def _transposed_weight(w):
     wt = wt.t().contiguous()
     if len(_wt_cache) > 512:
         _wt_cache.clear()
-    _wt_cache[key] = (stamp, wt)
+    _wt_cache[key] = (stamp, wt, weakref.ref(owner))
     return wt
 
 

@@ -1,8 +1,9 @@
 """Auxiliary subsystems: tar streaming, conversion mapping, flops profiler,
-rainbow convergence, bench distributed launch."""
+rainbow convergence, bench distributed launch and output dump."""
 
 import io
 import json
+import os
 import subprocess
 import sys
 import tarfile
@@ -203,14 +204,63 @@ def test_bench_distributed_launch_cpu():
            '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', '29701', str(REPO / 'bench.py'),
            '--config', 'tiny', '--steps', '2', '--warmup', '1']
+    # hide any GPUs: this is the CPU/gloo launch, and a 1-GPU machine has no
+    # device for local rank 1
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES='', HIP_VISIBLE_DEVICES='')
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600,
-                         cwd=str(REPO))
+                         cwd=str(REPO), env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [l for l in res.stdout.splitlines() if l.startswith('{')][-1]
     rec = json.loads(line)
     assert rec['n_gpus'] == 2
     assert rec['config']['parallelism'] == 'dp2'
     assert rec['value'] > 0
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """bench.py --dump-outputs: the last timed step's loss lands in
+    DIR/loss.npy as float32, identical across two runs with the same
+    arguments (seeded weights and data); --steps sets the timed step count
+    and the result line carries ms_per_step. --full is accepted."""
+    import numpy as np
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES='', HIP_VISIBLE_DEVICES='')
+    losses = []
+    for name, extra in (('a', []), ('b', ['--full'])):
+        out = tmp_path / name
+        cmd = [sys.executable, str(REPO / 'bench.py'), '--gpus', '1',
+               '--config', 'tiny', '--steps', '3', '--warmup', '1',
+               '--dump-outputs', str(out), *extra]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=300,
+                             cwd=str(REPO), env=env)
+        assert res.returncode == 0, res.stderr[-2000:]
+        rec = json.loads(
+            [l for l in res.stdout.splitlines() if l.startswith('{')][-1])
+        assert rec['steps'] == 3 and rec['ms_per_step'] > 0
+        assert [p.name for p in out.iterdir()] == ['loss.npy']
+        loss = np.load(out / 'loss.npy')
+        assert loss.dtype == np.float32 and np.isfinite(loss).all()
+        losses.append(loss)
+    assert np.array_equal(losses[0], losses[1])
+
+
+def test_weight_caches_reject_recycled_storage():
+    """The per-step W^T / bf16-cast caches key on (data_ptr, shape). A new
+    parameter that lands on a freed one's address with the same shape and
+    version must not be served the old entry; the same parameter and fresh
+    slices of it must still hit."""
+    from dalle_pytorch_amd.ops import fp8
+    p = torch.nn.Parameter(torch.randn(32, 16))
+    assert fp8._transposed_weight(p) is fp8._transposed_weight(p)
+    assert fp8._transposed_weight(p[:16]) is fp8._transposed_weight(p[:16])
+    assert fp8._cached_bf16(p) is fp8._cached_bf16(p)
+    # what address reuse produces: q's key maps to the entry p left behind
+    q = torch.nn.Parameter(torch.randn(32, 16))
+    for cache in (fp8._wt_cache, fp8._cast_cache):
+        cache[(q.data_ptr(), tuple(q.shape))] = \
+            cache[(p.data_ptr(), tuple(p.shape))]
+    qb = q.detach().to(torch.bfloat16)
+    assert torch.equal(fp8._transposed_weight(q), qb.t())
+    assert torch.equal(fp8._cached_bf16(q), qb)
 
 
 def test_clip_train_and_rerank(tmp_path):
