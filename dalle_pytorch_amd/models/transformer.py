@@ -21,9 +21,11 @@ from dalle_pytorch_amd.models.attention import (
     Attention, SparseAttention, SparseConvCausalAttention, SparseAxialCausalAttention)
 from dalle_pytorch_amd.models.positional import build_dalle_rotary_table
 from dalle_pytorch_amd.ops import geglu
-from dalle_pytorch_amd.ops.fp8 import fp8_linear
+from dalle_pytorch_amd.ops.fp8 import fp8_linear, linear_geglu, linear_geglu_ok
 from dalle_pytorch_amd.ops.fused import (token_shift, token_shift_supported,
-                                          layer_norm, add_scaled)
+                                          layer_norm, layer_norm_fused,
+                                          ln_shift, ln_shift_supported,
+                                          add_scaled)
 
 
 def _as_tuple(val, depth=1):
@@ -118,9 +120,39 @@ class PreNorm(nn.Module):
         self.norm_out = nn.LayerNorm(dim) if sandwich else nn.Identity()
         self.fn = fn
 
-    def forward(self, x, **kwargs):
-        y = layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
-        y = self.fn(y, **kwargs)
+    def fuses_dres(self, x):
+        """Whether forward(x, dres=...) can fold a residual-stream gradient
+        into the input norm's backward (the reversible executor asks)."""
+        return layer_norm_fused(x)
+
+    def _shift_child(self, x, kwargs):
+        """The PreShiftToken under this norm when LN + shift can run as one
+        kernel for this call (training-shape, uncached), else None."""
+        wrap = self.fn
+        shift = wrap.fn if isinstance(wrap, CachedAs) else None
+        if (isinstance(shift, PreShiftToken) and kwargs.get('cache') is None
+                and x.dim() == 3 and x.shape[1] >= shift.text_len
+                and ln_shift_supported(x)):
+            return shift
+        return None
+
+    def forward(self, x, dres=None, **kwargs):
+        """``dres`` (reversible replay only, see fuses_dres): gradient of
+        the residual stream at x; x.grad then comes back as dres + the
+        branch's own gradient, saving the executor's eager add."""
+        shift = self._shift_child(x, kwargs)
+        if shift is not None:
+            # LN + token shift in one pass; PreShiftToken's inner fn takes
+            # the shifted rows directly (it gets no cache / cache_key, as on
+            # PreShiftToken's own uncached path)
+            y = ln_shift(x, self.norm.weight, self.norm.bias, self.norm.eps,
+                         shift.text_len, shift.image_size, dres)
+            inner = {k: v for k, v in kwargs.items() if k != 'cache'}
+            y = shift.fn(y, **inner)
+        else:
+            y = layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps,
+                           dres)
+            y = self.fn(y, **kwargs)
         if isinstance(self.norm_out, nn.LayerNorm):
             y = layer_norm(y, self.norm_out.weight, self.norm_out.bias,
                            self.norm_out.eps)
@@ -147,8 +179,12 @@ class FeedForward(nn.Module):
         )
 
     def forward(self, x, cache=None, cache_key=None):
-        x = fp8_linear(self.net[0], x)
-        x = self.net[2](self.net[1](x))
+        if linear_geglu_ok(self.net[0], x):
+            # one autograd node: the ff1 bias gradient comes out of geglu_bwd
+            x = linear_geglu(self.net[0], x)
+        else:
+            x = self.net[1](fp8_linear(self.net[0], x))
+        x = self.net[2](x)
         return fp8_linear(self.net[3], x)
 
 

@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from dalle_pytorch_amd.ops.dispatch import hip_module, using_eager_fallback
+from dalle_pytorch_amd.ops.fused import fusion_enabled, geglu_bwd_colsum
 
 _FORCED = None
 FP8_MAX = 448.0
@@ -220,6 +221,59 @@ def fp8_linear(linear_module, x):
     if _fast_dgrad_ok(x, w):
         return _FastDgradLinearFn.apply(x.contiguous(), w, linear_module.bias)
     return linear_module(x)
+
+
+class _LinearGegluFn(torch.autograd.Function):
+    """geglu(linear(x)) as one autograd node, so the backward can take the
+    linear's bias gradient from geglu_bwd's column partials instead of a
+    separate reduce over the [rows, 2H] gradient it has just written. The
+    GEMM choice (fp8 / bf16), weight caches, dgrad and wgrad are those of
+    _Fp8LinearFn / _FastDgradLinearFn."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ext = hip_module()
+        bb = bias if bias.dtype == torch.bfloat16 else bias.to(torch.bfloat16)
+        x2 = x.reshape(-1, x.shape[-1])
+        if _fp8_ok(x, weight):
+            xq, xs = _quant(x2, ext)
+            wq, ws = _quant_weight(weight, ext)
+            h = torch._scaled_mm(xq, wq.t(), scale_a=xs, scale_b=ws,
+                                 bias=bb, out_dtype=torch.bfloat16)
+        else:
+            h = F.linear(x, _cached_bf16(weight), bb)
+        h = h.reshape(-1, weight.shape[0])
+        out = ext.geglu_fwd(h)
+        ctx.save_for_backward(x2, weight, h)
+        ctx.bias_dtype = bias.dtype
+        return out.reshape(*x.shape[:-1], weight.shape[0] // 2)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, weight, h = ctx.saved_tensors
+        do2 = dout.reshape(-1, dout.shape[-1]).contiguous()
+        dh, db = geglu_bwd_colsum(h, do2)
+        wt = _transposed_weight(weight)
+        dx = (dh @ wt.t()).reshape(*dout.shape[:-1], weight.shape[1])
+        dw = dh.t() @ x2.to(dh.dtype)
+        return dx, dw.to(weight.dtype), db.to(ctx.bias_dtype)
+
+
+def linear_geglu_ok(linear_module, x):
+    """The fused linear -> GEGLU node applies where the linear would take
+    one of the custom-backward paths anyway and the GEGLU kernels apply."""
+    w = linear_module.weight
+    n_out = w.shape[0]
+    h8 = n_out // 16
+    return (fusion_enabled('FF1_BIAS') and linear_module.bias is not None
+            and (_fp8_ok(x, w) or _fast_dgrad_ok(x, w))
+            and n_out % 16 == 0 and (h8 % 256 == 0 or 256 % h8 == 0))
+
+
+def linear_geglu(linear_module, x):
+    """geglu(linear_module(x)); callers check linear_geglu_ok first."""
+    return _LinearGegluFn.apply(x.contiguous(), linear_module.weight,
+                                linear_module.bias)
 
 
 def fp8_linear_raw(x, weight, bias):

@@ -1934,6 +1934,51 @@ void resls_bwd_kernel(const short* __restrict__ dout, const short* __restrict__ 
   for (int e = 0; e < 8; ++e) dg_part[prow * dim + ch + e] = dg[e];
 }
 
+// Reversible replay tail in one pass (same structure as resls_bwd): given the
+// replayed raw branch output o, the block output y and the upstream gradient
+// d, writes the reconstructed input x_rec = y - gamma * o (fp32, one
+// rounding, the exact inverse form of resls_fwd), the branch gradient
+// d_o = gamma * d, and the per-block dgamma partials of d * o. Replaces the
+// eager scale-cast / mul / sub chain and its autograd backward.
+__global__ __launch_bounds__(256)
+void rev_replay_kernel(const short* __restrict__ o, const short* __restrict__ y,
+                       const short* __restrict__ d,
+                       const float* __restrict__ gamma,
+                       short* __restrict__ xrec, short* __restrict__ dout,
+                       float* __restrict__ dg_part,   // [gridDim.x * rpp, dim]
+                       long rows, int dim) {
+  const int cpr = dim >> 3;
+  const int rpp = 256 / cpr;
+  const int rg = threadIdx.x / cpr;
+  const int ch = (threadIdx.x % cpr) * 8;
+  float g[8], dg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  #pragma unroll
+  for (int e = 0; e < 8; ++e) g[e] = gamma[ch + e];
+  for (long r = (long)blockIdx.x * rpp + rg; r < rows;
+       r += (long)gridDim.x * rpp) {
+    const long base = r * dim + ch;
+    int4v ov = *reinterpret_cast<const int4v*>(o + base);
+    int4v yv = *reinterpret_cast<const int4v*>(y + base);
+    int4v dv = *reinterpret_cast<const int4v*>(d + base);
+    const short* os = reinterpret_cast<const short*>(&ov);
+    const short* ys = reinterpret_cast<const short*>(&yv);
+    const short* ds_ = reinterpret_cast<const short*>(&dv);
+    short xo[8], go[8];
+    #pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float of = bf2f(os[e]), df = bf2f(ds_[e]);
+      xo[e] = f2bf(bf2f(ys[e]) - g[e] * of);
+      go[e] = f2bf(g[e] * df);
+      dg[e] += df * of;
+    }
+    *reinterpret_cast<int4v*>(xrec + base) = *reinterpret_cast<int4v*>(xo);
+    *reinterpret_cast<int4v*>(dout + base) = *reinterpret_cast<int4v*>(go);
+  }
+  const long prow = (long)blockIdx.x * rpp + rg;
+  #pragma unroll
+  for (int e = 0; e < 8; ++e) dg_part[prow * dim + ch + e] = dg[e];
+}
+
 // ---------------------------------------------------------------------------
 // Decode prelude: residual-apply + LayerNorm + optional token-shift for one
 // decode token, fused (the decode step is bound by a ~5 us per-kernel
@@ -2253,6 +2298,61 @@ __global__ void geglu_bwd_bf16_kernel(const short* __restrict__ x,
       *reinterpret_cast<const int4v*>(da);
   *reinterpret_cast<int4v*>(dx + row * (2L * H) + H + i0) =
       *reinterpret_cast<const int4v*>(dg);
+}
+
+// geglu_bwd that also emits fp32 column partials of the gradient it writes
+// (the bias gradient of the linear that feeds the gate: a column sum over a
+// tensor this kernel has just produced, so the separate full-tensor reduce
+// disappears). Columns are fixed per thread and rows are strided over
+// (blockIdx.y, row group); latency is hidden by occupancy, as in
+// geglu_bwd_bf16_kernel (the grid is one resident wave of blocks). Each
+// (blockIdx.y, row group) slot owns one partial row of [2H], summed by one
+// small torch sum (same scheme as ln_bwd / resls_bwd). The per-element arithmetic is that of
+// geglu_bwd_bf16_kernel; the partials accumulate the ROUNDED values, i.e.
+// exactly what a reduce over dx would read.
+__global__ __launch_bounds__(256)
+void geglu_bwd_colsum_kernel(const short* __restrict__ x,
+                             const short* __restrict__ dout,
+                             short* __restrict__ dx,
+                             float* __restrict__ part,   // [gridDim.y*rpp, 2H]
+                             long rows, int H) {
+  const int cpr = H >> 3;                        // 16B chunks per half row
+  const int tpr = cpr < 256 ? cpr : 256;         // threads per row in a block
+  const int rpp = 256 / tpr;
+  const int rg = threadIdx.x / tpr;
+  const int i0 = (blockIdx.x * tpr + threadIdx.x % tpr) * 8;
+  const long rstride = (long)gridDim.y * rpp;
+  float sa[8], sg[8];
+  #pragma unroll
+  for (int e = 0; e < 8; ++e) { sa[e] = 0.f; sg[e] = 0.f; }
+
+  for (long row = (long)blockIdx.y * rpp + rg; row < rows; row += rstride) {
+    int4v av = *reinterpret_cast<const int4v*>(x + row * (2L * H) + i0);
+    int4v gv = *reinterpret_cast<const int4v*>(x + row * (2L * H) + H + i0);
+    int4v dv = *reinterpret_cast<const int4v*>(dout + row * (long)H + i0);
+    const short* a = reinterpret_cast<const short*>(&av);
+    const short* g = reinterpret_cast<const short*>(&gv);
+    const short* d = reinterpret_cast<const short*>(&dv);
+    short da[8], dg[8];
+    #pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float afv = bf2f(a[e]), gfv = bf2f(g[e]), dfv = bf2f(d[e]);
+      da[e] = f2bf(dfv * gelu_f(gfv));
+      dg[e] = f2bf(dfv * afv * gelu_grad_f(gfv));
+      sa[e] += bf2f(da[e]);
+      sg[e] += bf2f(dg[e]);
+    }
+    *reinterpret_cast<int4v*>(dx + row * (2L * H) + i0) =
+        *reinterpret_cast<const int4v*>(da);
+    *reinterpret_cast<int4v*>(dx + row * (2L * H) + H + i0) =
+        *reinterpret_cast<const int4v*>(dg);
+  }
+  float* pr = part + ((long)blockIdx.y * rpp + rg) * (2L * H);
+  #pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    pr[i0 + e] = sa[e];
+    pr[H + i0 + e] = sg[e];
+  }
 }
 
 template <typename T>
@@ -2860,12 +2960,23 @@ __global__ void shift_decode_kernel(
 // into a [cap, dim] buffer summed by ATen (no atomic contention).
 // ---------------------------------------------------------------------------
 
-template <int PER>
+// SHIFT=true fuses the training token shift into the store (ln_shift): the
+// values are those of the plain kernel, but each lane writes its channels
+// to the row where token_shift's forward gather would fetch them from (the
+// scatter form of token_shift_src, backward=0), and a row zero-fills its
+// own shifted slots that have no source. A lane's PER channels lie within
+// one channel quarter (16 lanes per quarter), so the choice is per lane.
+// Every output element is written exactly once.
+template <int PER, bool SHIFT = false>
 __global__ __launch_bounds__(256)
+// the shifted store costs two address registers, which at dim 1024 sit on
+// an occupancy step (82 vs 80 VGPRs): hold that width at the plain kernel's
+// 6 waves/SIMD (the allocator finds 80 without a spill)
+__attribute__((amdgpu_waves_per_eu(SHIFT && PER == 16 ? 6 : 1)))
 void ln_fwd_kernel(const short* __restrict__ x, const float* __restrict__ w,
                    const float* __restrict__ bia, short* __restrict__ y,
                    float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                   long rows, float eps) {
+                   long rows, float eps, int n, int text_len, int S) {
   // one wave per TWO rows, both rows' loads issued before either row's
   // compute: the row-serial form left HBM latency exposed (~3.9 TB/s)
   constexpr int per = PER;
@@ -2910,6 +3021,42 @@ void ln_fwd_kernel(const short* __restrict__ x, const float* __restrict__ w,
       rstd_out[row0 + rr] = rstd;
     }
     short* yr = y + (row0 + rr) * (long)dim;
+    bool keep = true;      // false: this lane's channels have no destination
+    bool zfill = false;    // this row's own slots for this lane get zeros
+    // per-lane element offset from the (wave-uniform) row base: stays a
+    // 32-bit offset off a scalar base when the shift moves the lane's row
+    unsigned loff = lane * per;
+    if constexpr (SHIFT) {
+      const int region = lane >> 4;          // 0, 1: shifted quarters
+      if (region < 2) {
+        // the row is wave-uniform: keep the position math on the scalar unit
+        const int pos = (int)((unsigned)__builtin_amdgcn_readfirstlane(
+            (int)(row0 + rr)) % (unsigned)n);
+        int dst = 1;                         // rows ahead of this one
+        if (pos < text_len) {
+          keep = pos + 1 < text_len;
+          zfill = pos == 0;
+        } else {
+          const int g = pos - text_len;
+          const int gr = g / S, gc = g - gr * S;
+          if (region == 0) {
+            keep = pos + S < n;
+            dst = S;
+            zfill = gr == 0;
+          } else {
+            keep = gc + 1 < S && pos + 1 < n;
+            zfill = gc == 0;
+          }
+        }
+        if (zfill) {
+          #pragma unroll
+          for (int i = 0; i < per; i += 8)
+            *reinterpret_cast<int4v*>(yr + lane * per + i) = int4v{0, 0, 0, 0};
+        }
+        loff += (unsigned)(dst * dim);
+      }
+    }
+    if (!keep) continue;
     #pragma unroll
     for (int i = 0; i < per; i += 8) {
       short out8[8];
@@ -2918,13 +3065,17 @@ void ln_fwd_kernel(const short* __restrict__ x, const float* __restrict__ w,
         const int d = lane * per + i + e;
         out8[e] = f2bf((vals[rr][i + e] - mu) * rstd * w[d] + bia[d]);
       }
-      *reinterpret_cast<int4v*>(yr + lane * per + i) =
+      *reinterpret_cast<int4v*>(yr + loff + i) =
           *reinterpret_cast<const int4v*>(out8);
     }
   }
 }
 
-template <int PER>
+// SHIFT=true reads dy through token_shift's transposed gather (the adjoint
+// of the shift fused into ln_fwd_kernel<PER, true>); DRES=true adds a
+// residual-stream gradient, dx = dres + (LN gradient), summed in fp32 and
+// rounded once.
+template <int PER, bool SHIFT = false, bool DRES = false>
 __global__ __launch_bounds__(256)
 void ln_bwd_kernel(const short* __restrict__ x, const short* __restrict__ dy,
                    const float* __restrict__ w,
@@ -2933,7 +3084,8 @@ void ln_bwd_kernel(const short* __restrict__ x, const short* __restrict__ dy,
                    short* __restrict__ dx,
                    float* __restrict__ dgamma_part,   // [cap, dim]
                    float* __restrict__ dbeta_part,
-                   long rows) {
+                   long rows, const short* __restrict__ dres,
+                   int n, int text_len, int S) {
   constexpr int per = PER;
   constexpr int dim = PER * 64;
   const int block_row0 = blockIdx.x * 4;
@@ -2951,13 +3103,23 @@ void ln_bwd_kernel(const short* __restrict__ x, const short* __restrict__ dy,
     const short* dyr = dy + row * dim;
     const float mu = mean_in[row];
     const float rstd = rstd_in[row];
+    bool dyzero = false;
+    if constexpr (SHIFT) {
+      const int pos = (int)((unsigned)row % (unsigned)n);
+      int srcpos;
+      token_shift_src(pos, lane * per * 2, n, text_len, S, dim, dim / 2, 1,
+                      &srcpos, &dyzero);
+      dyr += (long)(srcpos - pos) * dim;
+    }
 
     float xh[PER], g[PER];
     float s1 = 0.f, s2 = 0.f;
     #pragma unroll
     for (int i = 0; i < per; i += 8) {
       int4v xv = *reinterpret_cast<const int4v*>(xr + lane * per + i);
-      int4v dv = *reinterpret_cast<const int4v*>(dyr + lane * per + i);
+      int4v dv = int4v{0, 0, 0, 0};
+      if (!SHIFT || !dyzero)
+        dv = *reinterpret_cast<const int4v*>(dyr + lane * per + i);
       const short* xs = reinterpret_cast<const short*>(&xv);
       const short* ds_ = reinterpret_cast<const short*>(&dv);
       #pragma unroll
@@ -2985,9 +3147,19 @@ void ln_bwd_kernel(const short* __restrict__ x, const short* __restrict__ dy,
     #pragma unroll
     for (int i = 0; i < per; i += 8) {
       short out8[8];
-      #pragma unroll
-      for (int e = 0; e < 8; ++e)
-        out8[e] = f2bf((g[i + e] - s1 - xh[i + e] * s2) * rstd);
+      if constexpr (DRES) {
+        int4v rv = *reinterpret_cast<const int4v*>(
+            dres + row * (long)dim + lane * per + i);
+        const short* rs = reinterpret_cast<const short*>(&rv);
+        #pragma unroll
+        for (int e = 0; e < 8; ++e)
+          out8[e] = f2bf(bf2f(rs[e]) +
+                         (g[i + e] - s1 - xh[i + e] * s2) * rstd);
+      } else {
+        #pragma unroll
+        for (int e = 0; e < 8; ++e)
+          out8[e] = f2bf((g[i + e] - s1 - xh[i + e] * s2) * rstd);
+      }
       *reinterpret_cast<int4v*>(dxr + lane * per + i) =
           *reinterpret_cast<const int4v*>(out8);
     }
@@ -3300,6 +3472,46 @@ torch::Tensor geglu_bwd(torch::Tensor x, torch::Tensor dout) {
   return dx;
 }
 
+// geglu_bwd + column sums of dx ([2H] fp32). bf16 only; H/8 must tile a
+// 256-thread block (a multiple or a divisor of 256 chunks per half row).
+std::vector<torch::Tensor> geglu_bwd_colsum(torch::Tensor x, torch::Tensor dout) {
+  CHK(x.is_cuda() && x.is_contiguous() && dout.is_contiguous());
+  CHK(x.dtype() == torch::kBFloat16 && dout.dtype() == torch::kBFloat16);
+  const int H = (int)x.size(-1) / 2;
+  CHK(H > 0 && H % 8 == 0 && x.size(-1) == 2L * H && dout.size(-1) == H);
+  const int cpr = H / 8;
+  CHK(cpr % 256 == 0 || 256 % cpr == 0);
+  const long rows = x.numel() / (2L * H);
+  CHK(dout.numel() == rows * (long)H);
+  auto dx = torch::empty_like(x);
+  const int tpr = cpr < 256 ? cpr : 256;
+  const int rpp = 256 / tpr;
+  const int nbx = cpr / tpr;
+  // one resident wave of blocks: the row loop then has no tail
+  static const long resident = [] {
+    int per_cu = 0, dev = 0;
+    hipDeviceProp_t prop;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu, geglu_bwd_colsum_kernel, 256, 0) != hipSuccess ||
+        hipGetDevice(&dev) != hipSuccess ||
+        hipGetDeviceProperties(&prop, dev) != hipSuccess || per_cu < 1)
+      return 1024L;
+    return (long)per_cu * prop.multiProcessorCount;
+  }();
+  const long want = std::max<long>(resident / nbx, 1);
+  const long nby = std::max<long>(
+      std::min<long>((rows + rpp - 1) / rpp, want), 1);
+  auto part = torch::empty({nby * rpp, 2L * H},
+                           x.options().dtype(torch::kFloat32));
+  hipLaunchKernelGGL(geglu_bwd_colsum_kernel, dim3(nbx, nby), dim3(256), 0,
+                     cur_stream(),
+                     reinterpret_cast<const short*>(x.data_ptr()),
+                     reinterpret_cast<const short*>(dout.data_ptr()),
+                     reinterpret_cast<short*>(dx.data_ptr()),
+                     part.data_ptr<float>(), rows, H);
+  return {dx, part.sum(0)};
+}
+
 torch::Tensor fa_decode(torch::Tensor qkv, torch::Tensor kc, torch::Tensor vc,
                         std::optional<torch::Tensor> cosv,
                         std::optional<torch::Tensor> sinv,
@@ -3453,7 +3665,7 @@ std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor w,
                        wf.data_ptr<float>(), bf_.data_ptr<float>(),
                        reinterpret_cast<short*>(y.data_ptr()),
                        mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       rows, (float)eps);
+                       rows, (float)eps, 0, 0, 1);
   };
   switch (dim) {
     case 512: launch(ln_fwd_kernel<8>); break;
@@ -3484,7 +3696,8 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor x, torch::Tensor dy,
                        wf.data_ptr<float>(), mean.data_ptr<float>(),
                        rstd.data_ptr<float>(),
                        reinterpret_cast<short*>(dx.data_ptr()),
-                       dgp.data_ptr<float>(), dbp.data_ptr<float>(), rows);
+                       dgp.data_ptr<float>(), dbp.data_ptr<float>(), rows,
+                       (const short*)nullptr, 0, 0, 1);
   };
   switch (dim) {
     case 512: launch(ln_bwd_kernel<8>); break;
@@ -3496,6 +3709,102 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor x, torch::Tensor dy,
   auto dgamma = dgp.sum(0);
   auto dbeta = dbp.sum(0);
   return {dx, dgamma, dbeta};
+}
+
+// LayerNorm + training token shift in one pass: bitwise the result of
+// token_shift(ln_fwd(x)), without the intermediate tensor. x is [b, n, dim].
+std::vector<torch::Tensor> ln_shift_fwd(torch::Tensor x, torch::Tensor w,
+                                        torch::Tensor b, double eps,
+                                        int64_t text_len, int64_t image_size) {
+  CHK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.is_contiguous());
+  CHK(x.dim() == 3 && image_size >= 1 && text_len >= 0);
+  const int dim = x.size(-1);
+  const int n = x.size(1);
+  CHK(n >= text_len);
+  const long rows = x.numel() / dim;
+  CHK(rows < (1L << 31));   // the kernel does its row math in 32 bits
+  auto y = torch::empty_like(x);
+  auto mean = torch::empty({rows}, x.options().dtype(torch::kFloat32));
+  auto rstd = torch::empty_like(mean);
+  auto wf = w.to(torch::kFloat32).contiguous();
+  auto bf_ = b.to(torch::kFloat32).contiguous();
+  dim3 grid((rows + 7) / 8);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, cur_stream(),
+                       reinterpret_cast<const short*>(x.data_ptr()),
+                       wf.data_ptr<float>(), bf_.data_ptr<float>(),
+                       reinterpret_cast<short*>(y.data_ptr()),
+                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       rows, (float)eps, n, (int)text_len, (int)image_size);
+  };
+  switch (dim) {
+    case 512: launch(ln_fwd_kernel<8, true>); break;
+    case 1024: launch(ln_fwd_kernel<16, true>); break;
+    case 1536: launch(ln_fwd_kernel<24, true>); break;
+    case 2048: launch(ln_fwd_kernel<32, true>); break;
+    default: TORCH_CHECK(false, "ln_shift_fwd: unsupported dim ", dim);
+  }
+  return {y, mean, rstd};
+}
+
+// Backward of ln_fwd / ln_shift_fwd with the extras fused in: dy is read
+// through the shift's transposed gather when image_size > 0 (x is then
+// [b, n, dim]), and dres, when given, is added to dx in fp32.
+std::vector<torch::Tensor> ln_shift_bwd(torch::Tensor x, torch::Tensor dy,
+                                        torch::Tensor w, torch::Tensor mean,
+                                        torch::Tensor rstd,
+                                        std::optional<torch::Tensor> dres,
+                                        int64_t text_len, int64_t image_size) {
+  CHK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.is_contiguous());
+  CHK(dy.is_contiguous() && dy.dtype() == torch::kBFloat16 &&
+      dy.numel() == x.numel());
+  const bool shift = image_size > 0;
+  const bool has_res = dres.has_value();
+  CHK(shift || has_res);
+  const int dim = x.size(-1);
+  const long rows = x.numel() / dim;
+  CHK(mean.numel() == rows && rstd.numel() == rows);
+  int n = 0;
+  if (shift) {
+    CHK(x.dim() == 3 && text_len >= 0 && x.size(1) >= text_len);
+    CHK(rows < (1L << 31));
+    n = x.size(1);
+  }
+  const short* rp = nullptr;
+  if (has_res) {
+    CHK(dres->is_cuda() && dres->is_contiguous() &&
+        dres->dtype() == torch::kBFloat16 && dres->numel() == x.numel());
+    rp = reinterpret_cast<const short*>(dres->data_ptr());
+  }
+  auto dx = torch::empty_like(x);
+  const long cap = std::min<long>((rows + 3) / 4, 512);
+  auto dgp = torch::empty({cap * 4, (long)dim}, x.options().dtype(torch::kFloat32));
+  auto dbp = torch::empty_like(dgp);
+  auto wf = w.to(torch::kFloat32).contiguous();
+  dim3 grid(cap);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, cur_stream(),
+                       reinterpret_cast<const short*>(x.data_ptr()),
+                       reinterpret_cast<const short*>(dy.data_ptr()),
+                       wf.data_ptr<float>(), mean.data_ptr<float>(),
+                       rstd.data_ptr<float>(),
+                       reinterpret_cast<short*>(dx.data_ptr()),
+                       dgp.data_ptr<float>(), dbp.data_ptr<float>(), rows,
+                       rp, n, (int)text_len, (int)image_size);
+  };
+  #define LN_SB(PER)                                                    \
+    if (shift && has_res) launch(ln_bwd_kernel<PER, true, true>);       \
+    else if (shift)       launch(ln_bwd_kernel<PER, true, false>);      \
+    else                  launch(ln_bwd_kernel<PER, false, true>);
+  switch (dim) {
+    case 512: LN_SB(8); break;
+    case 1024: LN_SB(16); break;
+    case 1536: LN_SB(24); break;
+    case 2048: LN_SB(32); break;
+    default: TORCH_CHECK(false, "ln_shift_bwd: unsupported dim ", dim);
+  }
+  #undef LN_SB
+  return {dx, dgp.sum(0), dbp.sum(0)};
 }
 
 std::vector<torch::Tensor> dec_prelude(
@@ -3746,6 +4055,36 @@ std::vector<torch::Tensor> resls_bwd(torch::Tensor dout, torch::Tensor y,
   return {dy, dgp.sum(0)};
 }
 
+// -> {x_rec = y - gamma*o, d_o = gamma*d, dgamma = sum_rows(d*o) [dim] fp32}
+std::vector<torch::Tensor> rev_replay(torch::Tensor o, torch::Tensor gamma,
+                                      torch::Tensor y, torch::Tensor d) {
+  CHK(o.is_cuda() && o.dtype() == torch::kBFloat16 &&
+      y.dtype() == torch::kBFloat16 && d.dtype() == torch::kBFloat16);
+  CHK(o.is_contiguous() && y.is_contiguous() && d.is_contiguous() &&
+      gamma.is_contiguous());
+  CHK(gamma.dtype() == torch::kFloat32);
+  const int dim = o.size(-1);
+  CHK(dim == gamma.numel() && (dim & 7) == 0 && (dim >> 3) <= 256 &&
+      (256 % (dim >> 3)) == 0);
+  CHK(y.numel() == o.numel() && d.numel() == o.numel());
+  const long rows = o.numel() / dim;
+  auto xrec = torch::empty_like(o);
+  auto dout = torch::empty_like(o);
+  const int rpp = 256 / (dim >> 3);
+  const long nb = std::max<long>(std::min<long>((rows + rpp - 1) / rpp, 1024), 1);
+  auto dgp = torch::empty({nb * rpp, (long)dim},
+                          o.options().dtype(torch::kFloat32));
+  hipLaunchKernelGGL(rev_replay_kernel, dim3(nb), dim3(256), 0, cur_stream(),
+                     reinterpret_cast<const short*>(o.data_ptr()),
+                     reinterpret_cast<const short*>(y.data_ptr()),
+                     reinterpret_cast<const short*>(d.data_ptr()),
+                     gamma.data_ptr<float>(),
+                     reinterpret_cast<short*>(xrec.data_ptr()),
+                     reinterpret_cast<short*>(dout.data_ptr()),
+                     dgp.data_ptr<float>(), rows, dim);
+  return {xrec, dout, dgp.sum(0)};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("resls_fwd", &resls_fwd, "fused residual + per-channel scale fwd");
   m.def("resls_bwd", &resls_bwd, "fused residual + per-channel scale bwd");
@@ -3790,5 +4129,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_bwd", &ln_bwd, "fused LayerNorm backward");
   m.def("geglu_fwd", &geglu_fwd, "fused GEGLU forward");
   m.def("geglu_bwd", &geglu_bwd, "fused GEGLU backward");
+  m.def("geglu_bwd_colsum", &geglu_bwd_colsum,
+        "fused GEGLU backward + fp32 column sums of dx");
+  m.def("ln_shift_fwd", &ln_shift_fwd, "LayerNorm + token shift forward");
+  m.def("ln_shift_bwd", &ln_shift_bwd,
+        "LayerNorm backward with shifted dy and/or residual gradient",
+        py::arg("x"), py::arg("dy"), py::arg("w"), py::arg("mean"),
+        py::arg("rstd"), py::arg("dres") = py::none(),
+        py::arg("text_len") = 0, py::arg("image_size") = 0);
+  m.def("rev_replay", &rev_replay,
+        "reversible replay tail: x_rec, d_o, dgamma in one pass");
   m.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 bf16 layout probe");
 }
