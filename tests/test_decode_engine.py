@@ -131,7 +131,7 @@ def test_fused_decode_kernels_match_torch_path():
 def test_sk2_pack_layout():
     """The sk2 packed-weight layout must match the kernel's index math:
     element (lane, e) of chunk (nt, kc) is w[nt*16 + (lane&15),
-    kc*32 + (lane>>4)*8 + e] (hip_ops.hip sk2_kernel). Pure-CPU check of
+    kc*32 + (lane>>4)*8 + e] (decode.hip sk2_kernel). Pure-CPU check of
     the reshape/permute formula used by FastDecoder._sk2_pack."""
     N, K = 64, 1024
     w = torch.arange(N * K, dtype=torch.float32).reshape(N, K)

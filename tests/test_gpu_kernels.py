@@ -563,7 +563,7 @@ def test_fp8_linear_vs_bf16(ext, monkeypatch):
 def test_fa8_ladder_vs_oracle(ext, monkeypatch):
     """Opt-in 8-wave 32x32 ladder forward vs the fp32 oracle (dense causal,
     non-causal, key-masked, axial) — kept correct although the 16x16 kernel
-    is faster at D=64 (see the dispatch comment in hip_ops.hip)."""
+    is faster at D=64 (see the dispatch comment in attention.hip)."""
     monkeypatch.setenv('DALLE_AMD_FA8', '1')
     torch.manual_seed(21)
     for nq, nk, causal in ((256, 256, True), (1280, 1280, True),
