@@ -27,6 +27,8 @@ the model's dict-cache generation (itself verified bitwise-equal to
 uncached recomputation) across attention types, shift, stable, reversible.
 """
 
+import os
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -36,7 +38,8 @@ from dalle_pytorch_amd.ops.fused import layer_norm as fused_layer_norm
 from dalle_pytorch_amd.models import attention as attn_mod
 from dalle_pytorch_amd.models.transformer import CachedAs, NonCached, PreShiftToken
 from dalle_pytorch_amd.models.dalle import gumbel_sample
-from dalle_pytorch_amd.ops import attention_core
+from dalle_pytorch_amd.ops import (attention_core, geglu, hip_available,
+                                   hip_module)
 
 
 def _unwrap(module):
@@ -79,16 +82,63 @@ def _pattern_mask(leaf, seq_len, device):
     raise ValueError(f'unsupported attention {name}')
 
 
+class _DecodeLinear:
+    """One projection of the stack. ``w`` [N, K] and ``b`` (engine dtype)
+    serve prefill's F.linear; the single-token ``route`` is chosen once by
+    FastDecoder._linear, and only the tensors that route reads exist:
+
+    * ``sk2`` / ``sk2_fp8``: the weights-streaming decode GEMM on a
+      fragment-order pack (``pk``, or ``pk8`` = (e4m3 pack, amax/448)) with
+      the epilogue fused — ``mode`` 0 bias, 1 bias + GEGLU, 2 bias + fp32
+      out — and the fp32 bias ``b32``: one dispatch where hipBLASLt + eager
+      epilogues took two or three (see sk2_kernel);
+    * ``transposed``: hipBLASLt on the pre-transposed copy ``wT``, which
+      picks a plain-NN kernel instead of the slow transposed-B one at
+      M <= 128;
+    * ``linear``: F.linear, as in prefill.
+    """
+    __slots__ = ('w', 'b', 'mode', 'route', 'wT', 'pk', 'pk8', 'b32')
+
+    def __init__(self, w, b, mode):
+        self.w, self.b, self.mode = w, b, mode
+        self.route = 'linear'
+        self.wT = self.pk = self.pk8 = self.b32 = None
+
+    def linear(self, x):
+        y = F.linear(x, self.w, self.b)
+        return geglu(y) if self.mode == 1 else y
+
+    def __call__(self, x):
+        if self.route == 'linear':
+            return self.linear(x)
+        rows = x.numel() // x.shape[-1]
+        x2 = x.reshape(rows, x.shape[-1])
+        if self.route == 'transposed':
+            out = torch.addmm(self.b, x2, self.wT) if self.b is not None \
+                else x2 @ self.wT
+        else:
+            pk, wscale = self.pk8 if self.route == 'sk2_fp8' else (self.pk, 1.0)
+            out = hip_module().sk2(x2, pk, self.b32, *self.w.shape, self.mode,
+                                   wscale)
+        return out.view(*x.shape[:-1], out.shape[-1])
+
+
 class _LayerState:
-    __slots__ = ('leaf', 'info', 'pattern', 'k', 'v', 'ring', 'is_attn', 'w',
-                 'live', 'live_cnt')
+    __slots__ = ('leaf', 'info', 'pattern', 'k', 'v', 'ring', 'is_attn',
+                 'live', 'live_cnt', 'ln_w', 'ln_b', 'lno_w', 'lno_b',
+                 'scale', 'scale32', 'qkv', 'out', 'ff1', 'ff2')
 
 
 class FastDecoder:
-    """Static-shape decoder bound to one DALLE instance and batch size."""
+    """Static-shape decoder bound to one DALLE instance and batch size.
+
+    ``fused`` / ``sk2`` force the fused single-token kernels and the sk2
+    decode GEMMs off (or assert them on); None auto-detects ``fused`` and
+    reads ``sk2`` from DALLE_AMD_SK2 (default on). Every switch is fixed
+    here: each projection's GEMM route is chosen in this constructor."""
 
     def __init__(self, dalle, batch_size, device=None, dtype=None,
-                 use_graph=False):
+                 use_graph=False, fused=None, sk2=None):
         self.dalle = dalle
         self.b = batch_size
         self.device = device if device is not None else next(dalle.parameters()).device
@@ -114,76 +164,73 @@ class FastDecoder:
                 st = _LayerState()
                 st.leaf, st.info = _unwrap(wrap)
                 st.is_attn = is_attn
-                st.pattern = None
-                st.k = st.v = st.ring = None
-                st.live = st.live_cnt = None
-                if is_attn:
-                    leaf = st.leaf
-                    st.pattern = _pattern_mask(leaf, self.N, self.device)
-                    h, d = leaf.heads, leaf.dim_head
-                    st.k = torch.zeros(self.b, h, self.N, d, device=self.device,
-                                       dtype=self.dtype)
-                    st.v = torch.zeros_like(st.k)
-                if st.info['shift'] is not None:
-                    S = st.info['shift'].image_size
-                    dim = st.info['norm'].normalized_shape[0]
-                    st.ring = torch.zeros(self.b, S, dim // 2,
-                                          device=self.device, dtype=self.dtype)
-                st.w = self._materialize(st)
                 self.states.append(st)
 
-        # head weights, pre-cast once (the decode loop never re-casts)
-        cast = lambda t: None if t is None else \
-            t.detach().to(self.device, self.dtype)
-        castf = lambda t: None if t is None else \
-            t.detach().to(self.device, torch.float32)
-        head_ln, head_lin = dalle.to_logits[0], dalle.to_logits[1]
-        ntt, nit = dalle.num_text_tokens, dalle.num_image_tokens
-        w_full = cast(head_lin.weight)
-        b_full = cast(head_lin.bias)
-        self.head_w = {
-            'ln_w': cast(head_ln.weight), 'ln_b': cast(head_ln.bias),
-            'w': w_full, 'b': b_full,
-            # decode steps are always image positions: the logits mask there
-            # allows exactly the image-vocab rows, so generation projects
-            # against this slice only (~7x less head GEMM + sampling work)
-            'w_img': w_full[ntt:ntt + nit].contiguous(),
-            'b_img': None if b_full is None else b_full[ntt:ntt + nit].contiguous(),
-            'b_img32': castf(None if head_lin.bias is None
-                             else head_lin.bias[ntt:ntt + nit]),
-        }
-        if self.head_w['w_img'].dtype == torch.bfloat16:
-            self.head_w['w_img_pk'] = self._sk2_pack(self.head_w['w_img'])
-        else:
-            self.head_w['w_img_pk'] = None
-
-        from dalle_pytorch_amd.ops.dispatch import hip_available
-        self.offset_t = torch.zeros(1, dtype=torch.long, device=self.device)
-        self.key_arange = torch.arange(self.N, device=self.device)
         # fused single-token kernels need bf16 caches, d=64 and the extension
-        dims_ok = all((not st.is_attn) or st.leaf.dim_head == 64
-                      for st in self.states)
-        self._fused_decode = (self.device.type == 'cuda'
-                              and self.dtype == torch.bfloat16
-                              and self.N <= 4096 and dims_ok
-                              and hip_available())
-        self._graph = None
-        self._g_token = None
-        self._g_logits = None
-        if self._fused_decode:
-            self._build_live_tables()
-        import os as _os
-        self._sk2_on = (self._fused_decode
-                        and _os.environ.get('DALLE_AMD_SK2', '1') == '1')
+        can_fuse = (self.device.type == 'cuda'
+                    and self.dtype == torch.bfloat16 and self.N <= 4096
+                    and all(st.leaf.dim_head == 64
+                            for st in self.states if st.is_attn)
+                    and hip_available())
+        if fused and not can_fuse:
+            raise ValueError('fused decode needs cuda, bf16, dim_head 64, '
+                             'seq_len <= 4096 and the HIP extension')
+        self._fused_decode = can_fuse if fused is None else bool(fused)
+        if sk2 is None:
+            sk2 = os.environ.get('DALLE_AMD_SK2', '1') == '1'
+        self._sk2_on = self._fused_decode and bool(sk2)
         # the K=4096 ff2 is the one decode shape where hipBLASLt still wins
         # (14 us in-situ F.linear vs 17.9 us sk2 — sk2's ring drains on HBM
         # latency at only 64 blocks); default keeps ff2 on hipBLASLt
-        self._sk2_maxk = int(_os.environ.get('DALLE_AMD_SK2_MAXK', '2048'))
+        self._sk2_maxk = int(os.environ.get('DALLE_AMD_SK2_MAXK', '2048'))
+        self._fp8 = os.environ.get('DALLE_AMD_FP8_DECODE', '0') == '1'
         self._fused_prelude = self._fused_decode and all(
             st.info['norm_out'] is None
             and st.info['scale'] is not None
             and st.info['norm'].normalized_shape[0] in (512, 1024, 2048)
             for st in self.states)
+
+        for st in self.states:
+            st.pattern = None
+            st.k = st.v = st.ring = None
+            st.live = st.live_cnt = None
+            if st.is_attn:
+                leaf = st.leaf
+                st.pattern = _pattern_mask(leaf, self.N, self.device)
+                h, d = leaf.heads, leaf.dim_head
+                st.k = torch.zeros(self.b, h, self.N, d, device=self.device,
+                                   dtype=self.dtype)
+                st.v = torch.zeros_like(st.k)
+            if st.info['shift'] is not None:
+                S = st.info['shift'].image_size
+                dim = st.info['norm'].normalized_shape[0]
+                st.ring = torch.zeros(self.b, S, dim // 2,
+                                      device=self.device, dtype=self.dtype)
+            self._materialize(st)
+
+        # head weights, pre-cast once (the decode loop never re-casts)
+        head_ln, head_lin = dalle.to_logits[0], dalle.to_logits[1]
+        ntt, nit = dalle.num_text_tokens, dalle.num_image_tokens
+        self.head_ln_w = self._cast(head_ln.weight)
+        self.head_ln_b = self._cast(head_ln.bias)
+        self.head_w = self._cast(head_lin.weight)
+        self.head_b = self._cast(head_lin.bias)
+        # decode steps are always image positions: the logits mask there
+        # allows exactly the image-vocab rows, so generation projects
+        # against this slice (a view of head_w) only (~7x less head GEMM +
+        # sampling work)
+        self.head_img = self._linear(
+            self.head_w[ntt:ntt + nit],
+            None if head_lin.bias is None else head_lin.bias[ntt:ntt + nit],
+            mode=2, bf16=self.b in (16, 32, 64))
+
+        self.offset_t = torch.zeros(1, dtype=torch.long, device=self.device)
+        self.key_arange = torch.arange(self.N, device=self.device)
+        self._token_graph = self._step_graph = None
+        self._graph_key = None
+        self._out_buf = self._gen_ptr = None
+        if self._fused_decode:
+            self._build_live_tables()
 
     def _build_live_tables(self):
         """Per attention layer, per offset row: the indices of the keys the
@@ -208,12 +255,17 @@ class FastDecoder:
             st.live_cnt = cnt.contiguous()
 
     @staticmethod
+    def _sk2_shape_ok(N, K):
+        return N % 32 == 0 and K % 1024 == 0
+
+    @staticmethod
     def _sk2_pack(w):
         """Pack [N, K] bf16 into MFMA A-fragment order [N/16][K/32][lane][8]
         (lane = kgroup*16 + col) so the sk2 decode GEMM streams each weight
         tile as one contiguous region. None if the shape doesn't qualify."""
         N, K = w.shape
-        if N % 32 or K % 1024 or not w.is_cuda or w.dtype != torch.bfloat16:
+        if not FastDecoder._sk2_shape_ok(N, K) or not w.is_cuda \
+                or w.dtype != torch.bfloat16:
             return None
         return (w.reshape(N // 16, 16, K // 32, 4, 8)
                  .permute(0, 2, 3, 1, 4).contiguous())
@@ -225,7 +277,8 @@ class FastDecoder:
         the weight-bound decode GEMMs; opt-in via DALLE_AMD_FP8_DECODE=1
         (a quality trade — logits move ~0.1-1%% per element)."""
         N, K = w.shape
-        if N % 32 or K % 1024 or not w.is_cuda or w.dtype != torch.bfloat16:
+        if not FastDecoder._sk2_shape_ok(N, K) or not w.is_cuda \
+                or w.dtype != torch.bfloat16:
             return None
         amax = w.detach().abs().amax().float().clamp(min=1e-12)
         scale = amax / 448.0
@@ -235,108 +288,75 @@ class FastDecoder:
                .permute(0, 2, 3, 1, 4).contiguous())
         return pk, float(scale)
 
+    def _cast(self, t, dtype=None):
+        return None if t is None else \
+            t.detach().to(self.device, self.dtype if dtype is None else dtype)
+
+    def _linear(self, weight, bias, mode=0, fp8=False, bf16=False,
+                transposed=False):
+        """Build one projection and fix its single-token route. ``fp8`` /
+        ``bf16`` say whether the caller's row-count and max-K rules admit
+        that sk2 pack; every sk2 route further needs sk2 on (hence the fused
+        path) and a shape _sk2_pack accepts. ``transposed`` names the
+        fallback when no pack is taken."""
+        lin = _DecodeLinear(self._cast(weight), self._cast(bias), mode)
+        if self._sk2_on and fp8:
+            lin.pk8 = self._sk2_pack_fp8(lin.w)
+        if self._sk2_on and bf16 and lin.pk8 is None:
+            lin.pk = self._sk2_pack(lin.w)
+        if lin.pk8 is not None or lin.pk is not None:
+            lin.route = 'sk2_fp8' if lin.pk8 is not None else 'sk2'
+            lin.b32 = self._cast(bias, torch.float32)
+        elif transposed:
+            lin.route = 'transposed'
+            lin.wT = lin.w.t().contiguous()
+        return lin
+
     def _materialize(self, st):
         """Pre-cast this branch's weights to the engine dtype once: under
         autocast the casts would otherwise be captured into the decode graph
         and replayed for every token (measured ~30% of replay time)."""
-        cast = lambda t: None if t is None else \
-            t.detach().to(self.device, self.dtype)
-        castf = lambda t: None if t is None else \
-            t.detach().to(self.device, torch.float32)
         # LN weights stay fp32: the fused kernel takes fp32 affine directly
         # (a bf16 copy would be re-cast on every graph replay)
-        w = {'ln_w': castf(st.info['norm'].weight),
-             'ln_b': castf(st.info['norm'].bias),
-             'scale': cast(st.info['scale']),
-             'scale32': None if st.info['scale'] is None else
-             castf(st.info['scale']).reshape(-1).contiguous()}
+        st.ln_w = self._cast(st.info['norm'].weight, torch.float32)
+        st.ln_b = self._cast(st.info['norm'].bias, torch.float32)
+        st.scale = self._cast(st.info['scale'])
+        st.scale32 = None if st.info['scale'] is None else \
+            self._cast(st.info['scale'], torch.float32).reshape(-1).contiguous()
+        st.lno_w = st.lno_b = None
         if st.info['norm_out'] is not None:
-            w['lno_w'] = castf(st.info['norm_out'].weight)
-            w['lno_b'] = castf(st.info['norm_out'].bias)
-        castT = lambda t: None if t is None else \
-            t.detach().to(self.device, self.dtype).t().contiguous()
+            st.lno_w = self._cast(st.info['norm_out'].weight, torch.float32)
+            st.lno_b = self._cast(st.info['norm_out'].bias, torch.float32)
+        st.qkv = st.out = st.ff1 = st.ff2 = None
+        # measured on-box (scripts/bench_sk2.py): at <= 64 rows sk2 wins every
+        # decode shape up to _sk2_maxk; at 128 rows the MT=8 variants tie or
+        # lose to hipBLASLt except the geglu-fused ff1
+        r64 = self.b in (16, 32, 64)
+        r128 = r64 or self.b == 128
+        fits = lambda w: w.shape[1] <= self._sk2_maxk
         if st.is_attn:
-            w['qkv'] = cast(st.leaf.to_qkv.weight)
-            w['qkv_T'] = castT(st.leaf.to_qkv.weight)
-            w['qkv_pk'] = self._sk2_pack(w['qkv'])
-            w['out_w'] = cast(st.leaf.to_out[0].weight)
-            w['out_T'] = castT(st.leaf.to_out[0].weight)
-            w['out_pk'] = self._sk2_pack(w['out_w'])
-            if self._want_fp8_decode():
-                w['qkv_pk8'] = self._sk2_pack_fp8(w['qkv'])
-                w['out_w_pk8'] = self._sk2_pack_fp8(w['out_w'])
-            w['out_b'] = cast(st.leaf.to_out[0].bias)
-            w['out_b32'] = castf(st.leaf.to_out[0].bias)
+            qkv, out = st.leaf.to_qkv, st.leaf.to_out[0]
+            # the transposed copy is a hipBLASLt preference: GPU only
+            st.qkv = self._linear(qkv.weight, None, fp8=self._fp8 and r64,
+                                  bf16=r64 and fits(qkv.weight),
+                                  transposed=self.device.type == 'cuda')
+            # without the fused path attention's torch-op branch projects
+            # with F.linear for single tokens too
+            st.out = self._linear(out.weight, out.bias, fp8=self._fp8 and r64,
+                                  bf16=r64 and fits(out.weight),
+                                  transposed=self._fused_decode)
         else:
-            net = st.leaf.net
-            w['ff1_w'] = cast(net[0].weight)
-            w['ff1_pk'] = self._sk2_pack(w['ff1_w'])
+            ff1, ff2 = st.leaf.net[0], st.leaf.net[3]
+            # fp8 packs (opt-in) take both or neither — at half the weight
+            # bytes sk2 wins the K=4096 ff2 too
+            fp8 = self._fp8 and r128 and \
+                self._sk2_shape_ok(*ff1.weight.shape) and \
+                self._sk2_shape_ok(*ff2.weight.shape)
             # the geglu-fused epilogue (mode 1) needs N = 2 * ff2-in width
-            if w['ff1_pk'] is not None and net[0].weight.shape[0] % 64:
-                w['ff1_pk'] = None
-            w['ff1_b'] = cast(net[0].bias)
-            w['ff1_b32'] = castf(net[0].bias)
-            w['ff2_w'] = cast(net[3].weight)
-            w['ff2_pk'] = self._sk2_pack(w['ff2_w'])
-            if self._want_fp8_decode():
-                w['ff1_w_pk8'] = self._sk2_pack_fp8(w['ff1_w'])
-                w['ff2_w_pk8'] = self._sk2_pack_fp8(w['ff2_w'])
-            w['ff2_b'] = cast(net[3].bias)
-            w['ff2_b32'] = castf(net[3].bias)
-        return w
-
-    @staticmethod
-    def _want_fp8_decode():
-        import os
-        return os.environ.get('DALLE_AMD_FP8_DECODE', '0') == '1'
-
-    def _sk2_ok(self, rows, pk, mode=0, k_dim=0):
-        # measured on-box (scripts/bench_sk2.py): at 128 rows the MT=8
-        # variants tie or lose to hipBLASLt except the geglu-fused ff1;
-        # at <= 64 rows sk2 wins every decode shape
-        if not (self._sk2_on and pk is not None) or k_dim > self._sk2_maxk:
-            return False
-        if rows in (16, 32, 64):
-            return True
-        return rows == 128 and mode == 1
-
-    def _sk2(self, x, pk, bias32, N, K, mode, wscale=1.0):
-        """Weights-streaming decode GEMM on a pre-packed tile layout with
-        the epilogue (bias / geglu / fp32 head) fused — one dispatch where
-        hipBLASLt + eager epilogues took two or three (see sk2_kernel).
-        A uint8/e4m3 pack streams fp8 weights (wscale = its amax/448)."""
-        from dalle_pytorch_amd.ops.dispatch import hip_module
-        rows = x.numel() // K
-        out = hip_module().sk2(x.reshape(rows, K), pk, bias32, N, K, mode,
-                               wscale)
-        no = N // 2 if mode == 1 else N
-        return out.view(*x.shape[:-1], no)
-
-    def _lin_t(self, x, wT, bias):
-        """Decode linear with a pre-transposed weight: hipBLASLt picks a
-        plain-NN kernel instead of the slow transposed-B one at M<=128
-        (decode weights are static, so the transposed copy is free)."""
-        rows = x.numel() // x.shape[-1]
-        x2 = x.reshape(rows, x.shape[-1])
-        out = torch.addmm(bias, x2, wT) if bias is not None else x2 @ wT
-        return out.view(*x.shape[:-1], wT.shape[1])
-
-    def _lin(self, x, w, bias32, bias):
-        """Decode-step linear. The skinny-M weights-streaming kernel is kept
-        behind DALLE_AMD_SKINNY=1: measured on-box, the decode step is bound
-        by a ~5 us per-kernel execution floor (gen_kernel_stats profile), so
-        the 3-kernel skinny path (zero + gemm + cast) loses to one hipBLASLt
-        dispatch even though neither is near the weight-bandwidth floor."""
-        import os
-        rows = x.numel() // x.shape[-1]
-        if (self._fused_decode and rows <= 128 and x.shape[-1] % 32 == 0
-                and w.shape[0] % 4 == 0
-                and os.environ.get('DALLE_AMD_SKINNY', '0') == '1'):
-            from dalle_pytorch_amd.ops.dispatch import hip_module
-            out = hip_module().skinny_gemm(
-                x.reshape(rows, x.shape[-1]), w, bias32)
-            return out.view(*x.shape[:-1], w.shape[0])
-        return F.linear(x, w, bias)
+            st.ff1 = self._linear(ff1.weight, ff1.bias, mode=1, fp8=fp8,
+                                  bf16=r128 and ff1.weight.shape[0] % 64 == 0)
+            st.ff2 = self._linear(ff2.weight, ff2.bias, fp8=fp8,
+                                  bf16=r64 and fits(ff2.weight))
 
     # ----------------------------------------------------------- branches
 
@@ -352,69 +372,25 @@ class FastDecoder:
             return torch.cat((out, tail), dim=-1) if tail.shape[-1] else out
         return one(q), one(k), one(v)
 
-    def _proj(self, x, st_w, key, bias32_key, bias_key, mode=0):
-        """Single-token projection: sk2 on the packed weight when profitable,
-        else the measured-best hipBLASLt form for the shape."""
-        w = st_w[key]
-        rows = x.numel() // x.shape[-1]
-        pk8 = st_w.get(key + '_pk8')
-        if pk8 is not None and self._sk2_ok(rows, pk8[0], mode):
-            return self._sk2(x, pk8[0], st_w.get(bias32_key), w.shape[0],
-                             w.shape[1], mode, pk8[1])
-        pk = st_w.get(key[:-2] + '_pk') if key.endswith('_w') else \
-            st_w.get(key + '_pk')
-        if self._sk2_ok(rows, pk, mode, w.shape[1]):
-            return self._sk2(x, pk, st_w.get(bias32_key), w.shape[0],
-                             w.shape[1], mode)
-        return None
-
     def _ff_decode(self, st, y):
-        """Single-token feed-forward: geglu-fused sk2 ff1 when available,
-        hipBLASLt ff2 (measured faster than sk2 at K=4096). fp8 packs
-        (opt-in) take both — at half the weight bytes sk2 wins ff2 too."""
-        rows = y.numel() // y.shape[-1]
-        pk8_1, pk8_2 = st.w.get('ff1_w_pk8'), st.w.get('ff2_w_pk8')
-        if pk8_1 is not None and pk8_2 is not None \
-                and self._sk2_ok(rows, pk8_1[0], 1):
-            y = self._sk2(y, pk8_1[0], st.w['ff1_b32'],
-                          st.w['ff1_w'].shape[0], st.w['ff1_w'].shape[1],
-                          1, pk8_1[1])
-            return self._sk2(y, pk8_2[0], st.w['ff2_b32'],
-                             st.w['ff2_w'].shape[0], st.w['ff2_w'].shape[1],
-                             0, pk8_2[1])
-        if self._sk2_ok(rows, st.w['ff1_pk'], 1):
-            y = self._sk2(y, st.w['ff1_pk'], st.w['ff1_b32'],
-                          st.w['ff1_w'].shape[0], st.w['ff1_w'].shape[1], 1)
-        else:
-            from dalle_pytorch_amd.ops import geglu
-            y = geglu(self._lin(y, st.w['ff1_w'], st.w['ff1_b32'],
-                                st.w['ff1_b']))
-        if self._sk2_ok(rows, st.w['ff2_pk'], 0, st.w['ff2_w'].shape[1]):
-            return self._sk2(y, st.w['ff2_pk'], st.w['ff2_b32'],
-                             st.w['ff2_w'].shape[0], st.w['ff2_w'].shape[1],
-                             0)
-        return self._lin(y, st.w['ff2_w'], st.w['ff2_b32'], st.w['ff2_b'])
+        """Single-token feed-forward: by default geglu-fused sk2 ff1, then
+        hipBLASLt ff2 (measured faster than sk2 at K=4096)."""
+        return st.ff2(st.ff1(y))
 
     def _attn(self, st, x, offset_t, n):
         """x [b, n, dim] at positions offset..offset+n-1 (prefill has
         offset 0; decode has n == 1)."""
         leaf = st.leaf
         h, d = leaf.heads, leaf.dim_head
-        qkv = self._proj(x, st.w, 'qkv', None, None) if n == 1 else None
-        if qkv is None:
-            qkv = (self._lin_t(x, st.w['qkv_T'], None) if n == 1
-                   else F.linear(x, st.w['qkv']))
+        qkv = st.qkv(x) if n == 1 else st.qkv.linear(x)
         if n == 1 and self._fused_decode:
-            from dalle_pytorch_amd.ops.dispatch import hip_module
             out = hip_module().fa_decode(
                 qkv.view(self.b, -1), st.k, st.v,
                 self.cos if self.rotary else None,
                 self.sin if self.rotary else None,
                 offset_t, st.pattern, leaf.scale,
                 st.live, st.live_cnt).view(self.b, 1, h * d)
-            y = self._proj(out, st.w, 'out_w', 'out_b32', 'out_b')
-            return y if y is not None else \
-                self._lin_t(out, st.w['out_T'], st.w['out_b'])
+            return st.out(out)
         q, k, v = (t.reshape(self.b, n, h, d).permute(0, 2, 1, 3)
                    for t in qkv.chunk(3, dim=-1))
         if self.rotary:
@@ -445,7 +421,7 @@ class FastDecoder:
             out = attention_core(q, k, v, leaf.scale, causal=True,
                                  static_mask=sm)
         out = out.permute(0, 2, 1, 3).reshape(self.b, n, h * d)
-        return F.linear(out, st.w['out_w'], st.w['out_b'])
+        return st.out.linear(out)
 
     def _shift_prefill(self, st, x, n):
         """Training-style token shift over the prompt + ring seeding
@@ -482,7 +458,6 @@ class FastDecoder:
         shift = st.info['shift']
         S, text_len = shift.image_size, shift.text_len
         if self._fused_decode:
-            from dalle_pytorch_amd.ops.dispatch import hip_module
             return hip_module().shift_decode(
                 x.reshape(self.b, -1).contiguous(), offset_t, st.ring,
                 text_len).view(self.b, 1, -1)
@@ -506,8 +481,7 @@ class FastDecoder:
 
     def _branch(self, st, x, offset_t, n):
         dim = x.shape[-1]
-        y = fused_layer_norm(x, st.w['ln_w'], st.w['ln_b'],
-                             st.info['norm'].eps)
+        y = fused_layer_norm(x, st.ln_w, st.ln_b, st.info['norm'].eps)
         if st.info['shift'] is not None:
             y = self._shift_prefill(st, y, n) if n > 1 else \
                 self._shift_decode(st, y, offset_t)
@@ -516,19 +490,16 @@ class FastDecoder:
         elif n == 1:
             y = self._ff_decode(st, y)
         else:
-            from dalle_pytorch_amd.ops import geglu
-            y = F.linear(y, st.w['ff1_w'], st.w['ff1_b'])
-            y = geglu(y)
-            y = F.linear(y, st.w['ff2_w'], st.w['ff2_b'])
+            y = st.ff2.linear(st.ff1.linear(y))
         if st.info['norm_out'] is not None:
-            y = F.layer_norm(y, (dim,), st.w['lno_w'], st.w['lno_b'],
+            y = F.layer_norm(y, (dim,), st.lno_w, st.lno_b,
                              st.info['norm_out'].eps)
         return y
 
     def _residual(self, x, st, y):
         # x + y*scale in one fused kernel (addcmul) instead of mul + add
-        if st.w['scale'] is not None:
-            return torch.addcmul(x, y, st.w['scale'])
+        if st.scale is not None:
+            return torch.addcmul(x, y, st.scale)
         return x + y
 
     def _body(self, st, z, offset_t):
@@ -537,7 +508,7 @@ class FastDecoder:
             return self._attn(st, z, offset_t, 1)
         return self._ff_decode(st, z)
 
-    def _prelude(self, ext, stream, pend, st, off):
+    def _prelude(self, ext, stream, pend, st):
         """One fused kernel: apply the previous branch's residual to the
         stream, LayerNorm it for this branch, token-shift if wrapped."""
         y, scale32 = pend
@@ -545,7 +516,7 @@ class FastDecoder:
         xn, z = ext.dec_prelude(
             stream.view(self.b, -1),
             None if y is None else y.view(self.b, -1),
-            scale32, st.w['ln_w'], st.w['ln_b'],
+            scale32, st.ln_w, st.ln_b,
             st.ring if shift is not None else None,
             self.offset_t, st.info['norm'].eps,
             shift.image_size if shift is not None else 1,
@@ -555,35 +526,28 @@ class FastDecoder:
     def _run_stack_decode_fused(self, x, off):
         """Decode step with fused preludes (the step is bound by a ~5 us
         per-kernel floor: residual+LN+shift as one kernel per branch)."""
-        from dalle_pytorch_amd.ops.dispatch import hip_module
         ext = hip_module()
-        it = iter(self.states)
         if not self.reversible:
             pend = (None, None)
-            last_scale = None
             for st in self.states:
-                x, z = self._prelude(ext, x, pend, st, off)
-                pend = (self._body(st, z, off), st.w['scale32'])
-                last_scale = st.w['scale']
-            y = pend[0]
-            return torch.addcmul(x, y, last_scale) if last_scale is not None \
-                else x + y
+                x, z = self._prelude(ext, x, pend, st)
+                pend = (self._body(st, z, off), st.scale32)
+            return self._residual(x, st, pend[0])
         x1, x2 = x, x.clone()
         pend2 = (None, None)
-        g_st = None
+        it = iter(self.states)
         for f_st in it:
             g_st = next(it)
-            x2, zf = self._prelude(ext, x2, pend2, f_st, off)
+            x2, zf = self._prelude(ext, x2, pend2, f_st)
             f_out = self._body(f_st, zf, off)
-            x1, zg = self._prelude(ext, x1, (f_out, f_st.w['scale32']), g_st, off)
+            x1, zg = self._prelude(ext, x1, (f_out, f_st.scale32), g_st)
             g_out = self._body(g_st, zg, off)
-            pend2 = (g_out, g_st.w['scale32'])
-        x2 = torch.addcmul(x2, pend2[0], g_st.w['scale']) \
-            if g_st.w['scale'] is not None else x2 + pend2[0]
+            pend2 = (g_out, g_st.scale32)
+        x2 = self._residual(x2, g_st, pend2[0])
         return (x1 + x2) / 2
 
     def _run_stack(self, x, offset_t, n):
-        if n == 1 and getattr(self, '_fused_prelude', False):
+        if n == 1 and self._fused_prelude:
             return self._run_stack_decode_fused(x, offset_t)
         if not self.reversible:
             it = iter(self.states)
@@ -600,29 +564,24 @@ class FastDecoder:
             x2 = self._residual(x2, g_st, self._branch(g_st, x1, offset_t, n))
         return (x1 + x2) / 2
 
-    def _head(self, x, position_mask_rows):
+    def _head_norm(self, x):
         d = self.dalle
         if d.stable:
             x = x / x.amax(dim=-1, keepdim=True)
-        x = F.layer_norm(x, (x.shape[-1],), self.head_w['ln_w'],
-                         self.head_w['ln_b'], d.to_logits[0].eps)
-        logits = F.linear(x, self.head_w['w'], self.head_w['b'])
-        lm = d.logits_mask[0].to(self.device).index_select(0, position_mask_rows)
+        return F.layer_norm(x, (x.shape[-1],), self.head_ln_w, self.head_ln_b,
+                            d.to_logits[0].eps)
+
+    def _head(self, x, position_mask_rows):
+        logits = F.linear(self._head_norm(x), self.head_w, self.head_b)
+        lm = self.dalle.logits_mask[0].to(self.device) \
+            .index_select(0, position_mask_rows)
         return logits.masked_fill(lm.unsqueeze(0), -torch.finfo(logits.dtype).max)
 
     def _head_img(self, x):
         """Image-vocab-only head for decode steps: an image position's logits
         mask allows exactly the image-vocab rows, so projecting against that
         slice is equivalent and ~7x cheaper (plus top-k/gumbel shrink with it)."""
-        d = self.dalle
-        if d.stable:
-            x = x / x.amax(dim=-1, keepdim=True)
-        x = F.layer_norm(x, (x.shape[-1],), self.head_w['ln_w'],
-                         self.head_w['ln_b'], d.to_logits[0].eps)
-        y = self._proj(x, self.head_w, 'w_img', 'b_img32', 'b_img', mode=2)
-        return y if y is not None else \
-            self._lin(x, self.head_w['w_img'], self.head_w['b_img32'],
-                      self.head_w['b_img'])
+        return self.head_img(self._head_norm(x))
 
     # ----------------------------------------------------------- prefill
 
@@ -653,10 +612,10 @@ class FastDecoder:
 
     # ------------------------------------------------------------- step
 
-    def step(self, token):
+    def step(self, token, image_head=False):
         """One decode step: image-token ids [b] at position offset ->
-        logits [b, total_tokens] (or [b, num_image_tokens] in the generate
-        loop's image-head mode); advances the offset."""
+        logits [b, total_tokens] (or [b, num_image_tokens] with
+        ``image_head``, the generate loop's mode); advances the offset."""
         d = self.dalle
         off = self.offset_t
         emb = d.image_emb(token).unsqueeze(1)
@@ -666,7 +625,7 @@ class FastDecoder:
                 .reshape(1, -1, emb.shape[-1])
             emb = emb + full.index_select(1, g)
         x = self._run_stack(emb.to(self.dtype), off, 1)
-        if getattr(self, '_img_head', False):
+        if image_head:
             logits = self._head_img(x)[:, 0]
         else:
             logits = self._head(x, off)[:, 0]
@@ -690,7 +649,6 @@ class FastDecoder:
             f'decoder built for batch {self.b}, got {nb} (guided={guided})'
         was_training = d.training
         d.eval()
-        self._img_head = True
         text = text[:, :d.text_seq_len]
         if guided:
             # null-conditioned half: zeroed text (forward's null_cond path
@@ -708,9 +666,8 @@ class FastDecoder:
             # only when a capture-baked constant changes — per-call
             # recapture leaked the old graph pool (~74 MB/call, soak-tested)
             # and cost ~100 ms of capture per batch.
-            if getattr(self, '_graph_key', None) != sample_args:
-                self._graph = None
-                self._g_token = self._g_next = None
+            if self._graph_key != sample_args:
+                self._token_graph = self._step_graph = None
                 self._out_buf = torch.empty(nb, d.image_seq_len,
                                             dtype=torch.long, device=self.device)
                 self._gen_ptr = torch.zeros(1, dtype=torch.long,
@@ -737,7 +694,6 @@ class FastDecoder:
                 token = step_fn(token, *sample_args)
             images = d.vae.decode(self._out_buf)
         finally:
-            self._img_head = False
             d.train(was_training)
         return images
 
@@ -746,7 +702,7 @@ class FastDecoder:
                 [st.v.clone() if st.v is not None else None for st in self.states],
                 [st.ring.clone() if st.ring is not None else None for st in self.states],
                 self.offset_t.clone(),
-                self._gen_ptr.clone() if getattr(self, '_gen_ptr', None) is not None else None)
+                self._gen_ptr.clone() if self._gen_ptr is not None else None)
 
     def _restore(self, snap):
         ks, vs, rings, off, ptr = snap
@@ -767,12 +723,11 @@ class FastDecoder:
         whole thing is graph-capturable (RNG advances via the graph-safe
         philox state), so a generation step replays with ZERO eager kernels."""
         feed = torch.cat((token, token), dim=0) if guided else token
-        logits = self.step(feed).float()
+        logits = self.step(feed, image_head=True).float()
         if guided:
             cond, null = logits[:nb], logits[nb:]
             logits = null + (cond - null) * cond_scale
         if self._fused_decode and logits.shape[-1] <= 8192:
-            from dalle_pytorch_amd.ops.dispatch import hip_module
             noise = torch.rand_like(logits)   # graph-capture-safe philox
             # the sampler writes the next-token feed buffer IN PLACE and
             # appends to the sequence buffer itself: no index_copy_ kernel
@@ -789,44 +744,41 @@ class FastDecoder:
         self._gen_ptr += 1
         return nxt
 
+    def _capture(self, fn, token):
+        """Capture ``fn(static token)`` -> (graph, static token, static out),
+        already replayed once for ``token``."""
+        g_token = token.clone()
+        snap = self._snapshot()     # warmup mutates caches/rings/offset
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                fn(g_token)
+        torch.cuda.current_stream().wait_stream(s)
+        self._restore(snap)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            g_out = fn(g_token)
+        # capture records without executing: run the real step once
+        graph.replay()
+        return graph, g_token, g_out
+
     def _graph_token_step(self, token, *args):
-        if self._graph is None:
-            self._g_token = token.clone()
-            snap = self._snapshot()
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self._g_next = self._token_step(self._g_token, *args)
-            torch.cuda.current_stream().wait_stream(s)
-            self._restore(snap)
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._g_next = self._token_step(self._g_token, *args)
-            self._graph.replay()
-            return self._g_next
-        if token is not self._g_token:   # the sampler writes the feed
-            self._g_token.copy_(token)   # buffer in place, so steady-state
-        self._graph.replay()             # replays skip this copy entirely
-        return self._g_next
+        if self._token_graph is None:
+            self._token_graph = self._capture(
+                lambda t: self._token_step(t, *args), token)
+            return self._token_graph[2]
+        graph, g_token, g_next = self._token_graph
+        if token is not g_token:         # the sampler writes the feed
+            g_token.copy_(token)         # buffer in place, so steady-state
+        graph.replay()                   # replays skip this copy entirely
+        return g_next
 
     def _graph_step(self, token):
-        if self._graph is None:
-            self._g_token = token.clone()
-            snap = self._snapshot()     # warmup mutates caches/rings/offset
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self._g_logits = self.step(self._g_token)
-            torch.cuda.current_stream().wait_stream(s)
-            self._restore(snap)
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._g_logits = self.step(self._g_token)
-            # capture records without executing: run the real step once
-            self._graph.replay()
-            return self._g_logits
-        self._g_token.copy_(token)
-        self._graph.replay()
-        return self._g_logits
+        if self._step_graph is None:
+            self._step_graph = self._capture(self.step, token)
+            return self._step_graph[2]
+        graph, g_token, g_logits = self._step_graph
+        g_token.copy_(token)
+        graph.replay()
+        return g_logits

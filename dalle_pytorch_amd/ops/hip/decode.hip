@@ -1,4 +1,4 @@
-// Single-token decode family: fused sampler, skinny weights-streaming GEMMs,
+// Single-token decode family: fused sampler, the sk2 weights-streaming GEMM,
 // the residual + LayerNorm + shift prelude, key-split decode attention and
 // the ring-buffer token shift.
 
@@ -114,117 +114,6 @@ void sample_topk_gumbel_kernel(
     // eager index_copy_ kernel + its index plumbing in the decode graph)
     if (seq != nullptr) seq[(long)row * S + *seq_ptr] = besti;
   }
-}
-
-// ---------------------------------------------------------------------------
-// Skinny-M GEMM: out[M, N] = x[M, K] @ W[N, K]^T (+ bias), M <= 128.
-//
-// The decode step's projections are M = batch (64..128) against multi-MB
-// weight matrices — pure weight-bandwidth problems that hipBLASLt runs at
-// ~520 GB/s (measured round 1, ~26% of generation). Here each 4-wave block
-// owns 64 rows of W and streams them once from HBM as MFMA A-fragments
-// (row-major 16 B loads); x is tiny (<=256 KB) and stays L2-resident, read
-// directly as B-fragments. K is split across blocks so every GEMM shape
-// fills the 256-CU chip; fp32 partials are reduced (+bias, bf16 cast) by a
-// trailing elementwise kernel.
-// ---------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256)
-void skinny_gemm_kernel(
-    const short* __restrict__ x,    // [M, K] bf16
-    const short* __restrict__ w,    // [N, K] bf16 (torch Linear layout)
-    float* __restrict__ outf,       // [M, N] fp32, pre-zeroed
-    int M, int N, int K, int kslice) {
-  // x slice staged once per block (M*kslice*2 <= 128 KB, host-enforced);
-  // +8 row pad despreads the B-frag banks
-  extern __shared__ short Xs[];
-  const int nt = blockIdx.x;        // n-tile (64 rows of W)
-  const int z = blockIdx.y;         // k-split index
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int lq = lane & 15, grp = lane >> 4;
-  const int n0 = nt * 64 + wave * 16;          // this wave's 16 W rows
-  const int k0 = z * kslice;
-  const int k1 = min(K, k0 + kslice);
-  const int kn = k1 - k0;
-  const int xpitch = kslice + 8;
-  const int mt_n = (M + 15) >> 4;
-  const bool single = gridDim.y == 1;
-
-  // cooperative x stage: 16B chunks, coalesced
-  for (int c = threadIdx.x; c < M * (kn >> 3); c += 256) {
-    const int m = c / (kn >> 3);
-    const int kk = (c - m * (kn >> 3)) * 8;
-    *reinterpret_cast<int4v*>(&Xs[m * xpitch + kk]) =
-        *reinterpret_cast<const int4v*>(x + (long)m * K + k0 + kk);
-  }
-  __syncthreads();
-
-  const short* wrow = w + (long)(n0 + lq) * K;  // A-frag: row = lane&15
-  const bool wok = n0 + lq < N;
-  f32x4 acc[8];
-  #pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = f32x4{0, 0, 0, 0};
-
-  // the ENTIRE k-slice's W fragments issued up front (kslice <= 512 ->
-  // <= 16 frags, 64 VGPRs): one-ahead prefetch left each HBM round-trip
-  // exposed (same disease as the decode PV loop, fixed the same way)
-  bf16x8 af[16];
-  const int ksteps = (kn + 31) / 32;
-  #pragma unroll
-  for (int t = 0; t < 16; ++t) {
-    if (t < ksteps && wok)
-      af[t] = *reinterpret_cast<const bf16x8*>(wrow + k0 + 32 * t + 8 * grp);
-    else
-      af[t] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  }
-  for (int t = 0; t < ksteps; ++t) {
-    #pragma unroll 4
-    for (int mt = 0; mt < mt_n; ++mt) {
-      const bf16x8 xf = *reinterpret_cast<const bf16x8*>(
-          &Xs[(mt * 16 + lq) * xpitch + 32 * t + 8 * grp]);
-      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[t], xf, acc[mt], 0, 0, 0);
-    }
-  }
-
-  // C[row = n (grp*4+r)][col = m (lane&15)]; K-split partial sums combine
-  // through fp32 atomics that stay in L2 (the [M, N] buffer is MBs at most)
-  for (int mt = 0; mt < mt_n; ++mt) {
-    const int m = mt * 16 + lq;
-    if (m >= M) continue;
-    const int n = nt * 64 + wave * 16 + grp * 4;
-    if (single) {
-      if (n + 3 < N) {
-        *reinterpret_cast<f32x4*>(outf + (long)m * N + n) = acc[mt];
-      } else {
-        for (int r = 0; r < 4 && n + r < N; ++r)
-          outf[(long)m * N + n + r] = acc[mt][r];
-      }
-    } else {
-      for (int r = 0; r < 4 && n + r < N; ++r)
-        atomicAdd(outf + (long)m * N + n + r, acc[mt][r]);
-    }
-  }
-}
-
-__global__ __launch_bounds__(256)
-void skinny_cast_kernel(
-    const float* __restrict__ outf,   // [M, N] fp32
-    const float* __restrict__ bias,   // [N] or null
-    short* __restrict__ out,          // [M, N] bf16
-    long MN, int N) {
-  const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i0 >= MN) return;
-  if (i0 + 3 >= MN) {
-    for (long i = i0; i < MN; ++i)
-      out[i] = f2bf(outf[i] + (bias ? bias[i % N] : 0.f));
-    return;
-  }
-  f32x4 v = *reinterpret_cast<const f32x4*>(outf + i0);
-  short o[4];
-  #pragma unroll
-  for (int e = 0; e < 4; ++e)
-    o[e] = f2bf(v[e] + (bias ? bias[(i0 + e) % N] : 0.f));
-  *reinterpret_cast<int2*>(out + i0) = *reinterpret_cast<int2*>(o);
 }
 
 // ---------------------------------------------------------------------------
@@ -1151,41 +1040,6 @@ torch::Tensor sample_topk_gumbel(torch::Tensor logits, torch::Tensor noise,
                      noise.contiguous().data_ptr<float>(),
                      out.data_ptr<long>(), seqp, ptrp, S, V, (int)k,
                      (float)(1.0 / temperature));
-  return out;
-}
-
-torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w, OptTensor bias) {
-  CHK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.is_contiguous());
-  CHK(w.dtype() == torch::kBFloat16 && w.is_contiguous());
-  const int M = x.size(0), K = x.size(1), N = w.size(0);
-  CHK(w.size(1) == K && M <= 128 && (K & 31) == 0);
-  const float* bp = nullptr;
-  torch::Tensor bf32;
-  if (bias.has_value()) {
-    bf32 = bias->detach().to(torch::kFloat32).contiguous();
-    bp = bf32.data_ptr<float>();
-  }
-  const int ntiles = (N + 63) / 64;
-  const int m_pad = ((M + 15) / 16) * 16;
-  int ksplit = std::min<int>({16, std::max(1, 512 / ntiles), (K + 63) / 64});
-  int kslice = ((K + ksplit - 1) / ksplit + 31) & ~31;
-  if (kslice > 512) kslice = 512;   // A-frag register budget (16 frags)
-  // x slice must fit LDS: m_pad * (kslice + 8) * 2 bytes
-  while ((long)m_pad * (kslice + 8) * 2 > 131072 && kslice > 32)
-    kslice = ((kslice / 2) + 31) & ~31;
-  ksplit = (K + kslice - 1) / kslice;
-  const int lds_bytes = m_pad * (kslice + 8) * 2;
-  auto outf = ksplit > 1
-      ? torch::zeros({(long)M, (long)N}, x.options().dtype(torch::kFloat32))
-      : torch::empty({(long)M, (long)N}, x.options().dtype(torch::kFloat32));
-  hipLaunchKernelGGL(skinny_gemm_kernel, dim3(ntiles, ksplit), dim3(256),
-                     lds_bytes, cur_stream(), bf16_cptr(x), bf16_cptr(w),
-                     outf.data_ptr<float>(), M, N, K, kslice);
-  auto out = torch::empty({(long)M, (long)N}, x.options());
-  const long MN = (long)M * N;
-  hipLaunchKernelGGL(skinny_cast_kernel, dim3((MN + 1023) / 1024), dim3(256),
-                     0, cur_stream(), outf.data_ptr<float>(), bp,
-                     bf16_ptr(out), MN, N);
   return out;
 }
 

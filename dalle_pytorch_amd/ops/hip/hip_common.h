@@ -9,7 +9,7 @@
 //   train_ops.hip  fused rope+QKV split, GEGLU, token-shift, LayerNorm,
 //                  residual scale, reversible replay, fp8 quantize
 //   decode.hip     the single-token decode family (key-split attention +
-//                  ring-buffer shift, skinny GEMMs, sampler)
+//                  ring-buffer shift, the sk2 decode GEMM, sampler)
 //   module.hip     the Python module definition
 // Written for wave64 / 8-XCD MI355X per the CDNA4 HIP guide — NOT a port of
 // any CUDA kernel.

@@ -98,6 +98,5 @@ torch::Tensor sample_topk_gumbel(torch::Tensor logits, torch::Tensor noise,
                                  int64_t k, double temperature,
                                  OptTensor out_tok, OptTensor seq,
                                  OptTensor seq_ptr);
-torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w, OptTensor bias);
 torch::Tensor sk2(torch::Tensor x, torch::Tensor wp, OptTensor bias, long N,
                   long K, long mode, double wscale);

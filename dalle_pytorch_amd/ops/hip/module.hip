@@ -23,9 +23,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("K"), py::arg("mode"), py::arg("wscale") = 1.0,
         "decode skinny GEMM on packed bf16/e4m3 weights "
         "(fused bias/geglu/fp32 head)");
-  m.def("skinny_gemm", &skinny_gemm,
-        "skinny-M weights-streaming GEMM (decode projections)",
-        py::arg("x"), py::arg("w"), py::arg("bias") = std::nullopt);
   m.def("dec_prelude", &dec_prelude,
         "fused decode residual + LayerNorm + token-shift");
   m.def("permlane_probe", &permlane_probe,

@@ -113,8 +113,8 @@ def test_fused_decode_kernels_match_torch_path():
 
     dec_f = FastDecoder(d, batch_size=2, dtype=torch.bfloat16)
     assert dec_f._fused_decode
-    dec_t = FastDecoder(d, batch_size=2, dtype=torch.bfloat16)
-    dec_t._fused_decode = False
+    dec_t = FastDecoder(d, batch_size=2, dtype=torch.bfloat16, fused=False)
+    assert not dec_t._fused_decode
 
     with torch.no_grad():
         a = dec_f.prefill(text)
@@ -166,10 +166,10 @@ def test_sk2_decode_path_matches_unpacked():
 
     dec_s = FastDecoder(d, batch_size=16, dtype=torch.bfloat16)
     assert dec_s._fused_decode and dec_s._sk2_on
-    assert dec_s.states[0].w.get('qkv_pk') is not None
-    assert dec_s.head_w.get('w_img_pk') is not None
-    dec_u = FastDecoder(d, batch_size=16, dtype=torch.bfloat16)
-    dec_u._sk2_on = False
+    assert dec_s.states[0].qkv.pk is not None
+    assert dec_s.head_img.pk is not None
+    dec_u = FastDecoder(d, batch_size=16, dtype=torch.bfloat16, sk2=False)
+    assert not dec_u._sk2_on
 
     with torch.no_grad():
         a = dec_s.prefill(text)
@@ -181,3 +181,123 @@ def test_sk2_decode_path_matches_unpacked():
     rel = (a[valid].float() - b[valid].float()).abs().max() / \
         b[valid].float().abs().max()
     assert rel < 5e-2, rel.item()
+
+
+def _linears(dec):
+    """Every _DecodeLinear of a decoder, as (name, instance)."""
+    out = [(f'{i}.{name}', getattr(st, name))
+           for i, st in enumerate(dec.states)
+           for name in (('qkv', 'out') if st.is_attn else ('ff1', 'ff2'))]
+    return out + [('head_img', dec.head_img)]
+
+
+def test_cpu_decoder_routes_are_plain():
+    """Without the fused path every projection decodes through F.linear and
+    holds nothing but the plain weight: no transposed copy, no pack."""
+    dec = FastDecoder(tiny_dalle(), batch_size=2)
+    assert not dec._fused_decode and not dec._sk2_on
+    assert len(_linears(dec)) == 2 * 4 + 1
+    for name, lin in _linears(dec):
+        assert lin.route == 'linear', (name, lin.route)
+        assert lin.wT is None and lin.pk is None and lin.pk8 is None, name
+        assert lin.b32 is None, name
+
+
+@pytest.fixture(scope='module')
+def sk2_dalle():
+    """Smallest model whose projections pass the sk2 pack gates
+    (K % 1024 == 0, dim_head 64)."""
+    torch.manual_seed(9)
+    return tiny_dalle(attn_types=('axial_row', 'axial_col'), depth=2, dim=1024,
+                      heads=16, dim_head=64).cuda().eval()
+
+
+@pytest.mark.gpu
+def test_decode_routes_fixed_at_construction(sk2_dalle, monkeypatch):
+    """The GEMM route of each projection is chosen in the constructor from
+    batch rows, weight shape and the switches, and only the tensors that
+    route reads are built."""
+    monkeypatch.delenv('DALLE_AMD_SK2', raising=False)
+    monkeypatch.delenv('DALLE_AMD_SK2_MAXK', raising=False)
+    monkeypatch.delenv('DALLE_AMD_FP8_DECODE', raising=False)
+
+    dec = FastDecoder(sk2_dalle, batch_size=16)
+    assert dec._fused_decode and dec._sk2_on and dec._fused_prelude
+    for st in dec.states:
+        if st.is_attn:
+            for lin in (st.qkv, st.out):
+                assert lin.route == 'sk2' and lin.mode == 0
+                assert lin.pk is not None and lin.wT is None
+        else:
+            assert st.ff1.route == 'sk2' and st.ff1.mode == 1
+            assert st.ff1.pk is not None
+            assert st.ff2.w.shape[1] == 4096      # K above the 2048 default
+            assert st.ff2.route == 'linear'
+            assert st.ff2.pk is None and st.ff2.wT is None
+    assert dec.head_img.route == 'sk2' and dec.head_img.mode == 2
+    assert dec.head_img.pk is not None
+    assert all(lin.pk8 is None for _, lin in _linears(dec))
+
+    dec = FastDecoder(sk2_dalle, batch_size=16, sk2=False)
+    assert dec._fused_decode and not dec._sk2_on
+    for st in dec.states:
+        if st.is_attn:
+            for lin in (st.qkv, st.out):
+                assert lin.route == 'transposed'
+                assert lin.wT is not None and lin.pk is None
+    assert all(lin.pk is None and lin.pk8 is None for _, lin in _linears(dec))
+
+    # the stale-flag case: sk2 may not outlive the fused path it depends on
+    dec = FastDecoder(sk2_dalle, batch_size=16, fused=False)
+    assert not dec._fused_decode and not dec._sk2_on
+    assert not dec._fused_prelude
+    for name, lin in _linears(dec):
+        assert not lin.route.startswith('sk2'), (name, lin.route)
+        assert lin.pk is None and lin.pk8 is None, name
+
+    monkeypatch.setenv('DALLE_AMD_SK2_MAXK', '4096')
+    dec = FastDecoder(sk2_dalle, batch_size=16)
+    for st in dec.states:
+        if not st.is_attn:
+            assert st.ff2.route == 'sk2' and st.ff2.pk is not None
+
+
+@pytest.mark.gpu
+def test_step_graph_and_token_graph_do_not_share(sk2_dalle):
+    """_graph_step (logits out) and _graph_token_step (sampling included)
+    each own their graph and static tensors: either order of use replays
+    the right one. Eager counterparts come from a second decoder."""
+    d = sk2_dalle
+    torch.manual_seed(13)
+    text = torch.randint(1, 50, (16, 8), device='cuda')
+    token = torch.randint(0, 64, (16,), device='cuda')
+    dec_g = FastDecoder(d, batch_size=16, dtype=torch.float32, use_graph=True)
+    dec_e = FastDecoder(d, batch_size=16, dtype=torch.float32)
+
+    def step_logits():
+        with torch.no_grad():
+            dec_g.prefill(text)
+            dec_e.prefill(text)
+            snap = dec_g._snapshot()
+            got = dec_g._graph_step(token).clone()
+            dec_g._restore(snap)
+            return got, dec_e.step(token)
+
+    def images():
+        torch.manual_seed(7)
+        got = dec_g.generate(text, temperature=1e-8, filter_thres=0.99)
+        torch.manual_seed(7)
+        return got, dec_e.generate(text, temperature=1e-8, filter_thres=0.99)
+
+    # step graph first, then the token graph through generate() ...
+    got, want = step_logits()
+    assert torch.allclose(got, want, atol=1e-3), (got - want).abs().max().item()
+    got, want = images()
+    assert torch.allclose(got, want, atol=1e-3), (got - want).abs().max().item()
+    # ... then the other way round, with the token graph still alive
+    got, want = step_logits()
+    assert torch.allclose(got, want, atol=1e-3), (got - want).abs().max().item()
+    assert dec_g._step_graph is not None and dec_g._token_graph is not None
+    assert dec_g._step_graph[0] is not dec_g._token_graph[0]
+    got, want = images()
+    assert torch.allclose(got, want, atol=1e-3), (got - want).abs().max().item()

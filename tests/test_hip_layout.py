@@ -14,7 +14,7 @@ from dalle_pytorch_amd.ops.hip import build as hip_build
 
 EXPORTS = {
     'resls_fwd', 'resls_bwd', 'quant_fp8', 'sample_topk_gumbel', 'amax_bf16',
-    'sk2', 'skinny_gemm', 'dec_prelude', 'permlane_probe', 'fa_fwd', 'fa_bwd',
+    'sk2', 'dec_prelude', 'permlane_probe', 'fa_fwd', 'fa_bwd',
     'rope_split_fwd', 'rope_split_bwd', 'token_shift', 'fa_decode',
     'shift_decode', 'ln_fwd', 'ln_bwd', 'geglu_fwd', 'geglu_bwd',
     'geglu_bwd_colsum', 'ln_shift_fwd', 'ln_shift_bwd', 'rev_replay',
@@ -26,7 +26,6 @@ DEFAULTS = {
     'fa_fwd': {'ax_t': '0', 'ax_S': '0', 'ax_axis': '-1'},
     'fa_bwd': {'grad_lse': 'None', 'ax_t': '0', 'ax_S': '0', 'ax_axis': '-1'},
     'sk2': {'wscale': '1.0'},
-    'skinny_gemm': {'bias': 'None'},
     'ln_shift_bwd': {'dres': 'None', 'text_len': '0', 'image_size': '0'},
     'sample_topk_gumbel': {'out_tok': 'None', 'seq': 'None',
                            'seq_ptr': 'None'},
