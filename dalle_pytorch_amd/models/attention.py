@@ -22,7 +22,6 @@ Semantics notes carried over from the reference (kept bit-for-bit):
   equality is pinned by tests/test_attention.py against independent oracles.
 """
 
-import os
 from math import ceil
 
 import torch
@@ -30,14 +29,16 @@ from torch import nn
 
 from dalle_pytorch_amd.models.positional import apply_rotary_to_qkv
 from dalle_pytorch_amd.ops import attention_core, axial_attention
+from dalle_pytorch_amd.ops.dispatch import env_flag
 from dalle_pytorch_amd.ops.fp8 import fp8_linear
 from dalle_pytorch_amd.ops.attention import build_tile_map
 from dalle_pytorch_amd.ops.rope import rope_split, rope_split_supported, trig_tables
 
 
-def _split_heads(t, h):
-    b, n, hd = t.shape
-    return t.reshape(b, n, h, hd // h).permute(0, 2, 1, 3)
+def grid_text_len(seq_len, image_size):
+    """Text positions (<bos> included) of a [text + image grid] sequence of
+    ``seq_len`` tokens whose last image token is never an input."""
+    return seq_len - image_size ** 2 + 1
 
 
 def _qkv_heads(x, to_qkv, h, dim_head, rotary_pos_emb, offset=0):
@@ -147,7 +148,26 @@ def block_sparse_mask(seq_len, block_size, text_seq_len, num_random_blocks,
 
 # ------------------------------------------------------------------- modules
 
-class Attention(nn.Module):
+class _AttentionBase(nn.Module):
+    """Hyper-parameters and the two projections every variant shares."""
+
+    def __init__(self, dim, seq_len, heads, dim_head, dropout, stable, causal):
+        super().__init__()
+        self.heads = heads
+        self.dim_head = dim_head
+        self.seq_len = seq_len
+        self.scale = dim_head ** -0.5
+        self.causal = causal
+        self.stable = stable  # numerically equivalent either way; kept for hparams parity
+        inner = heads * dim_head
+        self.to_qkv = nn.Linear(dim, inner * 3, bias=False)
+        self.to_out = nn.Sequential(nn.Linear(inner, dim), nn.Dropout(dropout))
+
+    def _project_out(self, out):
+        return self.to_out[1](fp8_linear(self.to_out[0], out))
+
+
+class Attention(_AttentionBase):
     """Full (optionally causal) multi-head self-attention with k/v cache.
 
     Parity target: reference attention.py:39-99. ``static_mask`` lets this
@@ -157,17 +177,8 @@ class Attention(nn.Module):
 
     def __init__(self, dim, seq_len, causal=True, heads=8, dim_head=64,
                  dropout=0., stable=False, static_mask=None):
-        super().__init__()
-        self.heads = heads
-        self.dim_head = dim_head
-        self.seq_len = seq_len
-        self.scale = dim_head ** -0.5
-        self.causal = causal
-        self.stable = stable  # numerically equivalent either way; kept for hparams parity
+        super().__init__(dim, seq_len, heads, dim_head, dropout, stable, causal)
         self.register_buffer('static_mask', static_mask, persistent=False)
-        inner = heads * dim_head
-        self.to_qkv = nn.Linear(dim, inner * 3, bias=False)
-        self.to_out = nn.Sequential(nn.Linear(inner, dim), nn.Dropout(dropout))
 
     def _masks(self, offset, n_q, n_k, device):
         if self.static_mask is None:
@@ -203,26 +214,14 @@ class Attention(nn.Module):
             causal=self.causal and offset == 0,
             key_mask=mask, static_mask=static, static_tiles=tiles,
             static_tiles_t=tiles_t, fold_heads=True)
-        return self.to_out[1](fp8_linear(self.to_out[0], out))
+        return self._project_out(out)
 
 
-class _StaticMaskSparseAttention(nn.Module):
+class _StaticMaskSparseAttention(_AttentionBase):
     """Shared machinery for the pattern-masked variants: one fused kernel
     call over the full sequence with a cached pattern mask + tile map. The
     kernel skips fully-masked (64q, 32k) tiles, so compute scales with the
     pattern's live area, not n^2."""
-
-    def __init__(self, dim, seq_len, heads, dim_head, dropout, stable, causal=True):
-        super().__init__()
-        self.heads = heads
-        self.dim_head = dim_head
-        self.seq_len = seq_len
-        self.scale = dim_head ** -0.5
-        self.causal = causal
-        self.stable = stable
-        inner = heads * dim_head
-        self.to_qkv = nn.Linear(dim, inner * 3, bias=False)
-        self.to_out = nn.Sequential(nn.Linear(inner, dim), nn.Dropout(dropout))
 
     # subclasses define: _mask_key(), _build_mask() -> [seq_len+1?, ...] bool
     def _pattern(self, n, device):
@@ -252,7 +251,7 @@ class _StaticMaskSparseAttention(nn.Module):
                              key_mask=km, static_mask=static,
                              static_tiles=tiles, static_tiles_t=tiles_t,
                              fold_heads=True)
-        return self.to_out[1](fp8_linear(self.to_out[0], out))
+        return self._project_out(out)
 
 
 class SparseAxialCausalAttention(_StaticMaskSparseAttention):
@@ -267,7 +266,7 @@ class SparseAxialCausalAttention(_StaticMaskSparseAttention):
         assert axis in (0, 1)
         self.axis = axis
         self.image_size = image_size
-        self.text_len = seq_len - image_size ** 2 + 1
+        self.text_len = grid_text_len(seq_len, image_size)
 
     def _mask_key(self):
         return ('axial', self.seq_len, self.image_size, self.axis)
@@ -294,8 +293,7 @@ class SparseAxialCausalAttention(_StaticMaskSparseAttention):
         force the round-1 masked-dense path for A/B comparison."""
         t = self.text_len
         b, n, _ = x.shape
-        if (n <= t or not self.causal
-                or os.environ.get('DALLE_AMD_AXIAL_MASKED', '0') == '1'):
+        if n <= t or not self.causal or env_flag('AXIAL_MASKED', False):
             return super().forward(x, mask=mask, rotary_pos_emb=rotary_pos_emb)
 
         q, k, v = _qkv_heads(x, self.to_qkv, self.heads, self.dim_head,
@@ -303,7 +301,7 @@ class SparseAxialCausalAttention(_StaticMaskSparseAttention):
         km = self._key_mask(mask, b, n, t, x.device)
         out = axial_attention(q, k, v, self.scale, t, self.image_size,
                               self.axis, key_mask=km)
-        return self.to_out[1](fp8_linear(self.to_out[0], out))
+        return self._project_out(out)
 
 
 class SparseConvCausalAttention(_StaticMaskSparseAttention):
@@ -320,7 +318,7 @@ class SparseConvCausalAttention(_StaticMaskSparseAttention):
         self.image_size = image_size
         self.kernel_size = kernel_size
         self.dilation = dilation
-        self.text_len = seq_len - image_size ** 2 + 1
+        self.text_len = grid_text_len(seq_len, image_size)
 
     def _mask_key(self):
         return ('conv', self.seq_len, self.image_size, self.kernel_size,

@@ -53,6 +53,11 @@ class Deterministic(nn.Module):
         self._had_gpu = False
         self._autocast = None   # (enabled, dtype) for 'cuda'
 
+    @property
+    def supports_residual(self):
+        """Whether the wrapped module takes ``residual=`` (a LayerScale)."""
+        return getattr(self.net, 'supports_residual', False)
+
     def record_rng(self, *tensors):
         self._cpu_state = torch.get_rng_state()
         if torch.cuda._initialized:
@@ -82,12 +87,12 @@ class Deterministic(nn.Module):
             return net(*args, **kwargs)
 
 
-def _residual_branch(det, inp, residual, record_rng, args):
-    """residual + det(inp): fused into one pass when the wrapped module is a
-    LayerScale (its `residual=` path routes through ops.fused.add_scaled)."""
-    if getattr(det.net, 'supports_residual', False):
-        return det(inp, residual=residual, record_rng=record_rng, **args)
-    return residual + det(inp, record_rng=record_rng, **args)
+def _add_branch(branch, inp, residual, **args):
+    """residual + branch(inp): one fused pass when the branch is a LayerScale
+    (its `residual=` path routes through ops.fused.add_scaled)."""
+    if getattr(branch, 'supports_residual', False):
+        return branch(inp, residual=residual, **args)
+    return residual + branch(inp, **args)
 
 
 class ReversibleBlock(nn.Module):
@@ -106,8 +111,8 @@ class ReversibleBlock(nn.Module):
     def forward(self, x1, x2, f_args={}, g_args={}):
         rec = self.training
         with torch.no_grad():
-            y1 = _residual_branch(self.f, x2, x1, rec, f_args)
-            y2 = _residual_branch(self.g, y1, x2, rec, g_args)
+            y1 = _add_branch(self.f, x2, x1, record_rng=rec, **f_args)
+            y2 = _add_branch(self.g, y1, x2, record_rng=rec, **g_args)
         return y1, y2
 
     @staticmethod
@@ -153,8 +158,7 @@ class ReversibleBlock(nn.Module):
     def _invert(self, det, inp, out, upstream, stream_grad, args):
         """rec = out - branch(inp) and the gradient reaching ``inp``'s stream:
         stream_grad + (upstream pushed through the branch)."""
-        if (getattr(det.net, 'supports_residual', False)
-                and fusion_enabled('REV_REPLAY')):
+        if det.supports_residual and fusion_enabled('REV_REPLAY'):
             return self._replay_fused(det, inp, out, upstream, stream_grad,
                                       args)
         b_out, via = self._replay_grad(det, inp, upstream, args)
@@ -201,11 +205,8 @@ class SequentialSequence(nn.Module):
     def forward(self, x, **kwargs):
         args = route_args(self.args_route, kwargs, len(self.layers))
         for (f, g), (f_args, g_args) in zip(self.layers, args):
-            for branch, branch_args in ((f, f_args), (g, g_args)):
-                if getattr(branch, 'supports_residual', False):
-                    x = branch(x, residual=x, **branch_args)
-                else:
-                    x = x + branch(x, **branch_args)
+            x = _add_branch(f, x, x, **f_args)
+            x = _add_branch(g, x, x, **g_args)
         return x
 
 

@@ -13,19 +13,23 @@ from functools import partial
 from itertools import islice, cycle
 
 import torch
-import torch.nn.functional as F
 from torch import nn
 
 from dalle_pytorch_amd.models.reversible import ReversibleSequence, SequentialSequence
 from dalle_pytorch_amd.models.attention import (
-    Attention, SparseAttention, SparseConvCausalAttention, SparseAxialCausalAttention)
+    Attention, SparseAttention, SparseConvCausalAttention,
+    SparseAxialCausalAttention, axial_mask, grid_text_len)
 from dalle_pytorch_amd.models.positional import build_dalle_rotary_table
 from dalle_pytorch_amd.ops import geglu
 from dalle_pytorch_amd.ops.fp8 import fp8_linear, linear_geglu, linear_geglu_ok
-from dalle_pytorch_amd.ops.fused import (token_shift, token_shift_supported,
+from dalle_pytorch_amd.ops.fused import (token_shift, token_shift_eager,
+                                          token_shift_supported,
                                           layer_norm, layer_norm_fused,
                                           ln_shift, ln_shift_supported,
                                           add_scaled)
+
+
+_AXIAL_AXIS = {'axial_row': 0, 'axial_col': 1}
 
 
 def _as_tuple(val, depth=1):
@@ -213,25 +217,11 @@ class PreShiftToken(nn.Module):
         self.image_size = image_size
         self.seq_len = seq_len
         self.img_seq_len = image_size ** 2
-        self.text_len = seq_len - self.img_seq_len + 1
+        self.text_len = grid_text_len(seq_len, image_size)
 
     def _shift_full(self, x):
         """Training-shape shift, whole sequence at once (eager path)."""
-        b, n, c = x.shape
-        t, S, q = self.text_len, self.image_size, x.shape[-1] // 4
-        prev = x[:, :t - 1, :c // 2]
-        text = torch.cat((
-            torch.cat((x.new_zeros(b, 1, c // 2), prev), dim=1),
-            x[:, :t, c // 2:]), dim=-1)
-        img = x[:, t:]
-        ni = img.shape[1]
-        if ni == 0:
-            return text
-        g = F.pad(img, (0, 0, 0, S * S - ni)).view(b, S, S, c)
-        top = torch.cat((g.new_zeros(b, 1, S, q), g[:, :-1, :, :q]), dim=1)
-        left = torch.cat((g.new_zeros(b, S, 1, q), g[:, :, :-1, q:2 * q]), dim=2)
-        img = torch.cat((top, left, g[..., 2 * q:]), dim=-1)
-        return torch.cat((text, img.view(b, S * S, c)[:, :ni]), dim=1)
+        return token_shift_eager(x, self.text_len, self.image_size)
 
     def _seed_ring(self, x):
         """Ring of the last S image positions' raw (top, left) quarters,
@@ -362,9 +352,9 @@ class Transformer(nn.Module):
 
         pos_emb = None
         if rotary_emb:
-            img_seq_len = image_fmap_size ** 2
-            text_len = seq_len - img_seq_len + 1
-            pos_emb = build_dalle_rotary_table(dim_head, text_len, image_fmap_size)
+            pos_emb = build_dalle_rotary_table(
+                dim_head, grid_text_len(seq_len, image_fmap_size),
+                image_fmap_size)
         self.register_buffer('pos_emb', pos_emb)
 
     def forward(self, x, **kwargs):
@@ -378,13 +368,13 @@ class Transformer(nn.Module):
             return Attention(dim, stable=stable, **common)
         if attn_type == 'sparse':
             return SparseAttention(dim, **common)
-        if attn_type in ('axial_row', 'axial_col'):
+        if attn_type in _AXIAL_AXIS:
             if opt_inference:   # cache-friendly static-mask simulation
                 return Attention(dim, stable=stable,
                                  static_mask=self._get_attention_mask(attn_type),
                                  **common)
             return SparseAxialCausalAttention(
-                dim, axis=(0 if attn_type == 'axial_row' else 1),
+                dim, axis=_AXIAL_AXIS[attn_type],
                 image_size=S, stable=stable, **common)
         if attn_type == 'conv_like':
             return SparseConvCausalAttention(dim, image_size=S, stable=stable,
@@ -395,21 +385,9 @@ class Transformer(nn.Module):
         """Dense bool mask reproducing axial attention (reference
         transformer.py:333-350): text keys always visible; image keys only
         within the same grid row (axial_row) or column (axial_col)."""
-        img_seq_len = self.image_fmap_size ** 2
-        text_len = self.seq_len + 1 - img_seq_len
-        S = self.image_fmap_size
-        m = torch.zeros(self.seq_len, self.seq_len, dtype=torch.bool)
-        m[:, :text_len] = True
-        if attn_type == 'axial_row':
-            for row in range(S):
-                lo = text_len + row * S
-                hi = text_len + (row + 1) * S
-                m[lo:hi, lo:hi] = True
-        elif attn_type == 'axial_col':
-            for col in range(S):
-                lo = text_len + col
-                m[lo::S, lo::S] = True
-        else:
+        if attn_type not in _AXIAL_AXIS:
             raise ValueError(f'attention type "{attn_type}" cannot be simulated '
                              'with a static mask')
-        return m
+        S = self.image_fmap_size
+        return axial_mask(self.seq_len, grid_text_len(self.seq_len, S), S,
+                          _AXIAL_AXIS[attn_type])

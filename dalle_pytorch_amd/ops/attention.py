@@ -46,53 +46,6 @@ def _eager_attention(q, k, v, scale, causal, key_mask, static_mask,
     return out
 
 
-def _flash_bwd_composite(q, k, v, out, lse, dout, scale, causal, key_mask,
-                         static_mask, q_chunk=128, grad_lse=None):
-    """Flash-style backward at the torch level: recompute P per q-chunk from
-    the saved logsumexp, never materializing the full n x n matrix. All
-    GEMMs run in bf16 on rocBLAS MFMA paths (fp32 accumulation inside);
-    the P/dS elementwise math is fp32. The hand-written fa_bwd kernels are
-    the production path; this stays as the oracle-adjacent fallback for
-    extensions built without them."""
-    b, h, nq, d = q.shape
-    nk = k.shape[2]
-    diag = nk - nq
-    dq = torch.empty_like(q)
-    dk = torch.zeros(b, h, nk, d, dtype=torch.float32, device=q.device)
-    dv = torch.zeros_like(dk)
-    kT = k.transpose(-1, -2)
-    arange_k = torch.arange(nk, device=q.device)
-
-    for c0 in range(0, nq, q_chunk):
-        c1 = min(c0 + q_chunk, nq)
-        qc, oc, doc = q[:, :, c0:c1], out[:, :, c0:c1], dout[:, :, c0:c1]
-        lsec = lse[:, :, c0:c1]
-
-        s = torch.matmul(qc, kT).float() * scale              # [b,h,C,nk]
-        if causal:
-            cm = arange_k[None, :] > (torch.arange(c0, c1, device=q.device)[:, None] + diag)
-            s = s.masked_fill(cm, float('-inf'))
-        if key_mask is not None:
-            s = s.masked_fill(~key_mask[:, None, None, :], float('-inf'))
-        if static_mask is not None:
-            s = s.masked_fill(~static_mask[c0:c1], float('-inf'))
-
-        p = torch.exp(s - lsec.unsqueeze(-1))
-        p = torch.nan_to_num(p, nan=0.0)                      # -inf - -inf rows
-        pb = p.to(q.dtype)
-
-        dv += torch.matmul(pb.transpose(-1, -2), doc).float()
-        dp = torch.matmul(doc, v.transpose(-1, -2)).float()
-        Dc = (doc.float() * oc.float()).sum(dim=-1, keepdim=True)
-        if grad_lse is not None:
-            Dc = Dc - grad_lse[:, :, c0:c1].unsqueeze(-1)
-        ds = (p * (dp - Dc) * scale).to(q.dtype)
-        dq[:, :, c0:c1] = torch.matmul(ds, k)
-        dk += torch.matmul(ds.transpose(-1, -2), qc).float()
-
-    return dq, dk.to(q.dtype), dv.to(q.dtype)
-
-
 class _FlashAttention(torch.autograd.Function):
     """Binds the gfx950 flash-attention forward kernel (saves out +
     logsumexp); backward recomputes probabilities chunk-by-chunk — no
@@ -123,28 +76,17 @@ class _FlashAttention(torch.autograd.Function):
         ext = hip_module()
         if dlse is not None:
             dlse = dlse.contiguous().float()
-        if hasattr(ext, 'fa_bwd'):
-            # with fold_heads, out/dout stay in their contiguous [b,n,h,d]
-            # layout — the bwd kernels read them with bnhd strides directly
-            dq, dk, dv = ext.fa_bwd(
-                q, k, v, out, lse, dout.contiguous(),
-                ctx.scale, ctx.causal, ctx.key_mask, ctx.static_mask,
-                ctx.tile_map, ctx.tile_map_t, ctx.fold_heads, dlse,
-                *ctx.axial)
-        else:
-            if ctx.axial[2] >= 0:
-                raise RuntimeError('axial-mode backward needs the fa_bwd '
-                                   'kernel (extension built without it)')
-            if ctx.fold_heads:
-                out = out.permute(0, 2, 1, 3)
-                dout = dout.permute(0, 2, 1, 3)
-            dq, dk, dv = _flash_bwd_composite(
-                q, k, v, out, lse, dout.contiguous(), ctx.scale, ctx.causal,
-                ctx.key_mask, ctx.static_mask, grad_lse=dlse)
+        # with fold_heads, out/dout stay in their contiguous [b,n,h,d]
+        # layout — the bwd kernels read them with bnhd strides directly
+        dq, dk, dv = ext.fa_bwd(
+            q, k, v, out, lse, dout.contiguous(),
+            ctx.scale, ctx.causal, ctx.key_mask, ctx.static_mask,
+            ctx.tile_map, ctx.tile_map_t, ctx.fold_heads, dlse,
+            *ctx.axial)
         return (dq, dk, dv) + (None,) * 8
 
 
-def _hip_supported(q, k, causal, key_mask):
+def _hip_supported(q):
     if q.shape[-1] not in _SUPPORTED_HEAD_DIMS:
         return False
     if q.dtype != torch.bfloat16:
@@ -183,7 +125,7 @@ def attention_core(q, k, v, scale, causal=True, key_mask=None, static_mask=None,
     correctly through both outputs (the axial decomposition path).
     Returns [b, h, nq, d] or [b, nq, h*d] (+ lse).
     """
-    if using_eager_fallback(q) or not _hip_supported(q, k, causal, key_mask):
+    if using_eager_fallback(q) or not _hip_supported(q):
         if q.is_cuda and q.shape[-2] >= 32:
             key = (q.shape[-1], str(q.dtype))
             if key not in _warned_shapes:
@@ -220,7 +162,7 @@ def axial_attention(q, k, v, scale, text_len, image_size, axis, key_mask=None):
     """
     b, h, n, d = q.shape
     t, S = text_len, image_size
-    fused = (not using_eager_fallback(q) and _hip_supported(q, k, True, None)
+    fused = (not using_eager_fallback(q) and _hip_supported(q)
              and S & (S - 1) == 0 and n > t)
     if fused:
         if key_mask is not None:

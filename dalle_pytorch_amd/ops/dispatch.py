@@ -34,8 +34,14 @@ def hip_available() -> bool:
     return hip_module() is not None
 
 
+def env_flag(name, default) -> bool:
+    """The on/off switch ``DALLE_AMD_<name>``: '1' is on, anything else off,
+    ``default`` when unset. Read per call, so tests and A/B runs can flip it."""
+    return os.environ.get('DALLE_AMD_' + name, '1' if default else '0') == '1'
+
+
 def allow_eager_on_gpu() -> bool:
-    return os.environ.get('DALLE_AMD_ALLOW_EAGER', '0') == '1'
+    return env_flag('ALLOW_EAGER', False)
 
 
 def using_eager_fallback(tensor) -> bool:

@@ -15,14 +15,15 @@ Enable with DALLE_AMD_FP8=1 (or ``set_fp8_enabled(True)``; bench.py
 exposes ``--fp8``). Default OFF: the headline BASELINE numbers are bf16.
 """
 
-import os
 import weakref
 
 import torch
 import torch.nn.functional as F
 
-from dalle_pytorch_amd.ops.dispatch import hip_module, using_eager_fallback
-from dalle_pytorch_amd.ops.fused import fusion_enabled, geglu_bwd_colsum
+from dalle_pytorch_amd.ops.dispatch import (env_flag, hip_module,
+                                            using_eager_fallback)
+from dalle_pytorch_amd.ops.fused import (fusion_enabled, geglu_bwd_colsum,
+                                         geglu_colsum_tiles)
 
 _FORCED = None
 FP8_MAX = 448.0
@@ -36,30 +37,57 @@ def set_fp8_enabled(flag):
 def fp8_enabled():
     if _FORCED is not None:
         return _FORCED
-    return os.environ.get('DALLE_AMD_FP8', '0') == '1'
+    return env_flag('FP8', False)
 
 
-_w_cache = {}
 _generation = 0
 
 
-def _owner(w):
-    """The tensor that owns ``w``'s storage for cache purposes: the base
-    parameter for a view (fresh slices of one parameter share it), else
-    ``w`` itself. The per-step caches below key on (data_ptr, shape); each
-    entry also holds a weak reference to this owner, so an entry left by a
-    freed parameter is never served to a new one that the allocator placed
-    at the same address with the same shape and version."""
-    base = w._base
-    return base if base is not None else w
-
-
 def fp8_mark_step():
-    """Invalidate the per-step weight-quant cache. Call after optimizer
-    steps — parameter version counters are not reliably bumped by every
+    """Invalidate the per-step weight caches. Call after optimizer steps —
+    parameter version counters are not reliably bumped by every
     fused/foreach CUDA optimizer path."""
     global _generation
     _generation += 1
+
+
+class _StepCache:
+    """Per-step cache of one tensor derived from a weight by ``make(w)``:
+    the reversible recompute re-runs every forward with unchanged weights,
+    so derive once per (parameter, version, step).
+
+    Keyed by storage + shape, so fresh VIEWS of the same slice (the
+    split-vocab head re-slices its weight every step) hit too. Each entry
+    also holds a weak reference to the tensor that owns the storage — the
+    base parameter for a view, else ``w`` itself — so an entry left by a
+    freed parameter is never served to a new one that the allocator placed
+    at the same address with the same shape and version. Always key on the
+    MASTER parameter (stable storage), never on cast temporaries. At most
+    ``BOUND`` entries: a full cache empties itself."""
+
+    BOUND = 512
+
+    def __init__(self, make):
+        self.make = make
+        self.entries = {}
+
+    def __call__(self, w):
+        key = (w.data_ptr(), tuple(w.shape))
+        stamp = (w._version, _generation)
+        owner = w._base if w._base is not None else w
+        hit = self.entries.get(key)
+        if hit is not None and hit[0] == stamp and hit[2]() is owner:
+            return hit[1]
+        val = self.make(w)
+        if len(self.entries) >= self.BOUND:
+            self.entries.clear()
+        self.entries[key] = (stamp, val, weakref.ref(owner))
+        return val
+
+
+def _bf16(w):
+    w = w.detach()
+    return w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)
 
 
 def _quant(t, ext):
@@ -68,115 +96,14 @@ def _quant(t, ext):
     return ext.quant_fp8(t, scale), scale.squeeze()
 
 
-def _quant_weight(w, ext):
-    """Per-step cache: the reversible recompute re-runs every forward with
-    unchanged weights, so quantize once per (param, version). Keyed by
-    storage+shape so fresh VIEWS of the same slice (the split-vocab head
-    re-slices its weight every step) hit the cache too."""
-    key = (w.data_ptr(), tuple(w.shape))
-    hit = _w_cache.get(key)
-    stamp = (w._version, _generation)
-    owner = _owner(w)
-    if hit is not None and hit[0] == stamp and hit[3]() is owner:
-        return hit[1], hit[2]
-    wb = w.detach()
-    if wb.dtype != torch.bfloat16:
-        wb = wb.to(torch.bfloat16)
-    wq, ws = _quant(wb, ext)
-    _w_cache[key] = (stamp, wq, ws, weakref.ref(owner))
-    return wq, ws
-
-
-_wt_cache = {}
-_cast_cache = {}
-
-
-def _cached_bf16(w):
-    """Per-step cached bf16 copy of a master weight (what autocast's
-    per-autocast-region weight cache would provide)."""
-    if w.dtype == torch.bfloat16:
-        return w
-    key = (w.data_ptr(), tuple(w.shape))
-    stamp = (w._version, _generation)
-    hit = _cast_cache.get(key)
-    owner = _owner(w)
-    if hit is not None and hit[0] == stamp and hit[2]() is owner:
-        return hit[1]
-    wb = w.detach().to(torch.bfloat16)
-    if len(_cast_cache) > 512:
-        _cast_cache.clear()
-    _cast_cache[key] = (stamp, wb, weakref.ref(owner))
-    return wb
-
-
-def _transposed_weight(w):
-    """Per-step cached contiguous bf16 W^T: hipBLASLt runs dgrad ~15%
-    faster fed a transposed-view B operand (scripts/probe_dgrad.py:
-    ff1-dgrad 1261 -> 1460 TF/s). Keyed on the MASTER parameter (stable
-    storage), never on cast temporaries."""
-    key = (w.data_ptr(), tuple(w.shape))
-    stamp = (w._version, _generation)
-    hit = _wt_cache.get(key)
-    owner = _owner(w)
-    if hit is not None and hit[0] == stamp and hit[2]() is owner:
-        return hit[1]
-    wt = w.detach()
-    if wt.dtype != torch.bfloat16:
-        wt = wt.to(torch.bfloat16)
-    wt = wt.t().contiguous()
-    if len(_wt_cache) > 512:
-        _wt_cache.clear()
-    _wt_cache[key] = (stamp, wt, weakref.ref(owner))
-    return wt
-
-
-def _linear_backward(ctx, dout):
-    """Shared backward: transposed-weight dgrad, standard wgrad/bias."""
-    x2, weight = ctx.saved_tensors
-    do2 = dout.reshape(-1, dout.shape[-1]).contiguous()
-    wt = _transposed_weight(weight)
-    dx = (do2 @ wt.t()).reshape(*dout.shape[:-1], weight.shape[1])
-    dw = do2.t() @ x2.to(do2.dtype)
-    db = do2.sum(0) if ctx.has_bias else None
-    return dx, dw.to(weight.dtype), db
-
-
-class _FastDgradLinearFn(torch.autograd.Function):
-    """bf16 F.linear with the transposed-dgrad backward. Receives MASTER
-    weights (any float dtype) and casts inside, so the per-step caches key
-    on stable parameter storage."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        wb = _cached_bf16(weight)
-        bb = bias if (bias is None or bias.dtype == torch.bfloat16) \
-            else bias.to(torch.bfloat16)
-        ctx.save_for_backward(x.reshape(-1, x.shape[-1]), weight)
-        ctx.has_bias = bias is not None
-        return F.linear(x, wb, bb)
-
-    @staticmethod
-    def backward(ctx, dout):
-        return _linear_backward(ctx, dout)
-
-
-class _Fp8LinearFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        ext = hip_module()
-        shape = x.shape
-        x2 = x.reshape(-1, shape[-1])
-        xq, xs = _quant(x2, ext)
-        wq, ws = _quant_weight(weight, ext)
-        out = torch._scaled_mm(xq, wq.t(), scale_a=xs, scale_b=ws,
-                               bias=bias, out_dtype=torch.bfloat16)
-        ctx.save_for_backward(x2, weight)
-        ctx.has_bias = bias is not None
-        return out.reshape(*shape[:-1], weight.shape[0])
-
-    @staticmethod
-    def backward(ctx, dout):
-        return _linear_backward(ctx, dout)
+# (e4m3 weight, scale)
+_quant_weight = _StepCache(lambda w: _quant(_bf16(w), hip_module()))
+# bf16 copy of a master weight (what autocast's per-region weight cache
+# would provide)
+_bf16_weight = _StepCache(_bf16)
+# contiguous bf16 W^T: hipBLASLt runs dgrad ~15% faster fed a transposed-
+# view B operand (scripts/probe_dgrad.py: ff1-dgrad 1261 -> 1460 TF/s)
+_transposed_weight = _StepCache(lambda w: _bf16(w).t().contiguous())
 
 
 def _fp8_ok(x, weight):
@@ -208,42 +135,86 @@ def _fast_dgrad_ok(x, w):
             and w.shape[1] % 16 == 0 and torch.is_grad_enabled())
 
 
+def _gemm_forward(x, weight, bias):
+    """x @ weight^T + bias in bf16 -> (x as [rows, k], output [rows, n]):
+    the fp8 GEMM where ``_fp8_ok``, else F.linear on the cached bf16 weight.
+    ``weight`` is the MASTER parameter, ``bias`` None or already bf16."""
+    x2 = x.reshape(-1, x.shape[-1])
+    if _fp8_ok(x, weight):
+        xq, xs = _quant(x2, hip_module())
+        wq, ws = _quant_weight(weight)
+        out = torch._scaled_mm(xq, wq.t(), scale_a=xs, scale_b=ws,
+                               bias=bias, out_dtype=torch.bfloat16)
+    else:
+        wb = weight if weight.dtype == torch.bfloat16 else _bf16_weight(weight)
+        out = F.linear(x, wb, bias).reshape(-1, weight.shape[0])
+    return x2, out
+
+
+def _gemm_backward(do2, x2, weight, lead):
+    """(dx [*lead, k], dW) from the output gradient do2 [rows, n]:
+    transposed-weight dgrad, standard wgrad."""
+    wt = _transposed_weight(weight)
+    dx = (do2 @ wt.t()).reshape(*lead, weight.shape[1])
+    dw = do2.t() @ x2.to(do2.dtype)
+    return dx, dw.to(weight.dtype)
+
+
+def _bf16_bias(bias):
+    if bias is None or bias.dtype == torch.bfloat16:
+        return bias
+    return bias.to(torch.bfloat16)
+
+
+class _LinearFn(torch.autograd.Function):
+    """bf16 linear (fp8 forward GEMM where profitable) with the
+    transposed-dgrad backward. Receives MASTER weights (any float dtype)
+    and casts inside, so the per-step caches key on stable parameter
+    storage."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x2, out = _gemm_forward(x, weight, _bf16_bias(bias))
+        ctx.save_for_backward(x2, weight)
+        ctx.has_bias = bias is not None
+        return out.reshape(*x.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, weight = ctx.saved_tensors
+        do2 = dout.reshape(-1, dout.shape[-1]).contiguous()
+        dx, dw = _gemm_backward(do2, x2, weight, dout.shape[:-1])
+        return dx, dw, do2.sum(0) if ctx.has_bias else None
+
+
+def fp8_linear_raw(x, weight, bias, module=None):
+    """F.linear(x, weight, bias) through the fp8 forward path when
+    profitable, else in bf16 with the transposed-dgrad backward (raw-tensor
+    form for weight slices, e.g. the split-vocab CE head); else plain
+    F.linear — or ``module(x)`` when the tensors are a module's own."""
+    if (_fp8_ok(x, weight) or _fast_dgrad_ok(x, weight)) \
+            and weight.is_contiguous():
+        return _LinearFn.apply(x.contiguous(), weight, bias)
+    return F.linear(x, weight, bias) if module is None else module(x)
+
+
 def fp8_linear(linear_module, x):
-    """F.linear through the fp8 forward path when profitable; else a bf16
-    linear with the transposed-dgrad backward; else the module itself.
-    Drop-in for ``linear_module(x)``."""
-    w = linear_module.weight
-    if _fp8_ok(x, w):
-        bias = linear_module.bias
-        if bias is not None and bias.dtype != torch.bfloat16:
-            bias = bias.to(torch.bfloat16)
-        return _Fp8LinearFn.apply(x.contiguous(), w, bias)
-    if _fast_dgrad_ok(x, w):
-        return _FastDgradLinearFn.apply(x.contiguous(), w, linear_module.bias)
-    return linear_module(x)
+    """Drop-in for ``linear_module(x)`` on the fp8_linear_raw ladder; its
+    last resort is the module itself, so module hooks still fire."""
+    return fp8_linear_raw(x, linear_module.weight, linear_module.bias,
+                          linear_module)
 
 
 class _LinearGegluFn(torch.autograd.Function):
     """geglu(linear(x)) as one autograd node, so the backward can take the
     linear's bias gradient from geglu_bwd's column partials instead of a
     separate reduce over the [rows, 2H] gradient it has just written. The
-    GEMM choice (fp8 / bf16), weight caches, dgrad and wgrad are those of
-    _Fp8LinearFn / _FastDgradLinearFn."""
+    GEMMs and weight caches are _LinearFn's."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        ext = hip_module()
-        bb = bias if bias.dtype == torch.bfloat16 else bias.to(torch.bfloat16)
-        x2 = x.reshape(-1, x.shape[-1])
-        if _fp8_ok(x, weight):
-            xq, xs = _quant(x2, ext)
-            wq, ws = _quant_weight(weight, ext)
-            h = torch._scaled_mm(xq, wq.t(), scale_a=xs, scale_b=ws,
-                                 bias=bb, out_dtype=torch.bfloat16)
-        else:
-            h = F.linear(x, _cached_bf16(weight), bb)
-        h = h.reshape(-1, weight.shape[0])
-        out = ext.geglu_fwd(h)
+        x2, h = _gemm_forward(x, weight, _bf16_bias(bias))
+        out = hip_module().geglu_fwd(h)
         ctx.save_for_backward(x2, weight, h)
         ctx.bias_dtype = bias.dtype
         return out.reshape(*x.shape[:-1], weight.shape[0] // 2)
@@ -253,36 +224,20 @@ class _LinearGegluFn(torch.autograd.Function):
         x2, weight, h = ctx.saved_tensors
         do2 = dout.reshape(-1, dout.shape[-1]).contiguous()
         dh, db = geglu_bwd_colsum(h, do2)
-        wt = _transposed_weight(weight)
-        dx = (dh @ wt.t()).reshape(*dout.shape[:-1], weight.shape[1])
-        dw = dh.t() @ x2.to(dh.dtype)
-        return dx, dw.to(weight.dtype), db.to(ctx.bias_dtype)
+        dx, dw = _gemm_backward(dh, x2, weight, dout.shape[:-1])
+        return dx, dw, db.to(ctx.bias_dtype)
 
 
 def linear_geglu_ok(linear_module, x):
     """The fused linear -> GEGLU node applies where the linear would take
     one of the custom-backward paths anyway and the GEGLU kernels apply."""
     w = linear_module.weight
-    n_out = w.shape[0]
-    h8 = n_out // 16
     return (fusion_enabled('FF1_BIAS') and linear_module.bias is not None
             and (_fp8_ok(x, w) or _fast_dgrad_ok(x, w))
-            and n_out % 16 == 0 and (h8 % 256 == 0 or 256 % h8 == 0))
+            and geglu_colsum_tiles(w.shape[0]))
 
 
 def linear_geglu(linear_module, x):
     """geglu(linear_module(x)); callers check linear_geglu_ok first."""
     return _LinearGegluFn.apply(x.contiguous(), linear_module.weight,
                                 linear_module.bias)
-
-
-def fp8_linear_raw(x, weight, bias):
-    """F.linear(x, weight, bias) with the fp8 forward path when profitable
-    (raw-tensor form for weight slices, e.g. the split-vocab CE head)."""
-    if _fp8_ok(x, weight) and weight.is_contiguous():
-        if bias is not None and bias.dtype != torch.bfloat16:
-            bias = bias.to(torch.bfloat16)
-        return _Fp8LinearFn.apply(x.contiguous(), weight, bias)
-    if _fast_dgrad_ok(x, weight) and weight.is_contiguous():
-        return _FastDgradLinearFn.apply(x.contiguous(), weight, bias)
-    return F.linear(x, weight, bias)

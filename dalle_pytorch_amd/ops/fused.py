@@ -4,12 +4,11 @@ On gfx950 these are single HBM-bound passes (vectorized bf16x8 loads per the
 CDNA4 guide); on CPU the eager equivalents run.
 """
 
-import os
-
 import torch
 import torch.nn.functional as F
 
-from dalle_pytorch_amd.ops.dispatch import hip_module, using_eager_fallback
+from dalle_pytorch_amd.ops.dispatch import (env_flag, hip_module,
+                                            using_eager_fallback)
 
 
 class _GegluFn(torch.autograd.Function):
@@ -61,8 +60,39 @@ def token_shift(x, text_len, image_size):
 
 
 def token_shift_supported(x):
-    return (x.is_cuda and hip_module() is not None
+    return (not using_eager_fallback(x)
             and x.shape[-1] * x.element_size() % 64 == 0)
+
+
+def token_shift_eager(x, text_len, image_size):
+    """Eager training-shape token shift, whole sequence at once (same
+    contract as token_shift)."""
+    b, n, c = x.shape
+    t, S, q = text_len, image_size, c // 4
+    prev = x[:, :t - 1, :c // 2]
+    text = torch.cat((
+        torch.cat((x.new_zeros(b, 1, c // 2), prev), dim=1),
+        x[:, :t, c // 2:]), dim=-1)
+    img = x[:, t:]
+    ni = img.shape[1]
+    if ni == 0:
+        return text
+    g = F.pad(img, (0, 0, 0, S * S - ni)).view(b, S, S, c)
+    top = torch.cat((g.new_zeros(b, 1, S, q), g[:, :-1, :, :q]), dim=1)
+    left = torch.cat((g.new_zeros(b, S, 1, q), g[:, :, :-1, q:2 * q]), dim=2)
+    img = torch.cat((top, left, g[..., 2 * q:]), dim=-1)
+    return torch.cat((text, img.view(b, S * S, c)[:, :ni]), dim=1)
+
+
+def _rows_of_8(*tensors):
+    """The resls_* / rev_replay kernels' rule: bf16 rows on the kernel path,
+    8 channels per thread, and the dim/8 threads of a row tile a 256-thread
+    block."""
+    x = tensors[0]
+    c8, rest = divmod(x.shape[-1], 8)
+    return (x.is_cuda and all(t.dtype == torch.bfloat16 for t in tensors)
+            and not using_eager_fallback(x) and rest == 0
+            and 0 < c8 <= 256 and 256 % c8 == 0)
 
 
 class _AddScaledFn(torch.autograd.Function):
@@ -92,9 +122,7 @@ class _AddScaledFn(torch.autograd.Function):
 
 def add_scaled(x, y, gamma):
     """x + gamma * y (gamma broadcast over the last dim)."""
-    if (x.is_cuda and x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16
-            and not using_eager_fallback(x) and x.shape[-1] % 8 == 0
-            and x.shape[-1] // 8 <= 256 and 256 % (x.shape[-1] // 8) == 0):
+    if _rows_of_8(x, y):
         return _AddScaledFn.apply(x, y, gamma)
     return x + y * gamma.to(y.dtype)
 
@@ -102,8 +130,8 @@ def add_scaled(x, y, gamma):
 def fusion_enabled(name):
     """Off switches for the fused training-tail paths, for A/B runs and
     tests: DALLE_AMD_LN_SHIFT, DALLE_AMD_REV_REPLAY, DALLE_AMD_FF1_BIAS
-    (each default '1'; '0' restores the unfused path). Read per call."""
-    return os.environ.get('DALLE_AMD_' + name, '1') == '1'
+    (each default '1'; '0' restores the unfused path)."""
+    return env_flag(name, True)
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -203,35 +231,11 @@ def ln_shift(x, weight, bias, eps, text_len, image_size, dres=None):
     y = layer_norm(x, weight, bias, eps, dres)
     if token_shift_supported(y):
         return token_shift(y, text_len, image_size)
-    return _shift_full_eager(y, text_len, image_size)
-
-
-def _shift_full_eager(x, t, S):
-    """Eager training-shape token shift (same contract as token_shift)."""
-    b, n, c = x.shape
-    q = c // 4
-    prev = x[:, :t - 1, :c // 2]
-    text = torch.cat((
-        torch.cat((x.new_zeros(b, 1, c // 2), prev), dim=1),
-        x[:, :t, c // 2:]), dim=-1)
-    img = x[:, t:]
-    ni = img.shape[1]
-    if ni == 0:
-        return text
-    g = F.pad(img, (0, 0, 0, S * S - ni)).view(b, S, S, c)
-    top = torch.cat((g.new_zeros(b, 1, S, q), g[:, :-1, :, :q]), dim=1)
-    left = torch.cat((g.new_zeros(b, S, 1, q), g[:, :, :-1, q:2 * q]), dim=2)
-    img = torch.cat((top, left, g[..., 2 * q:]), dim=-1)
-    return torch.cat((text, img.view(b, S * S, c)[:, :ni]), dim=1)
+    return token_shift_eager(y, text_len, image_size)
 
 
 def rev_replay_supported(o, y, d):
-    """Same conditions as add_scaled's kernel path."""
-    return (o.is_cuda and o.dtype == torch.bfloat16
-            and y.dtype == torch.bfloat16 and d.dtype == torch.bfloat16
-            and o.shape == y.shape == d.shape
-            and not using_eager_fallback(o) and o.shape[-1] % 8 == 0
-            and o.shape[-1] // 8 <= 256 and 256 % (o.shape[-1] // 8) == 0)
+    return o.shape == y.shape == d.shape and _rows_of_8(o, y, d)
 
 
 def rev_replay(o, gamma, y, d):
@@ -257,11 +261,17 @@ def rev_replay(o, gamma, y, d):
     return x_rec, d_o, dg.reshape(gamma.shape).to(gamma.dtype)
 
 
+def geglu_colsum_tiles(width):
+    """geglu_bwd_colsum's tiling rule for a GEGLU input of ``width`` = 2H
+    channels: the H/8 column groups of a half row are a multiple or a
+    divisor of the 256-thread block."""
+    h8, rest = divmod(width, 16)
+    return rest == 0 and h8 > 0 and (h8 % 256 == 0 or 256 % h8 == 0)
+
+
 def geglu_bwd_colsum_supported(x):
-    h8 = x.shape[-1] // 16
-    return (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] % 16 == 0
-            and h8 > 0 and not using_eager_fallback(x)
-            and (h8 % 256 == 0 or 256 % h8 == 0))
+    return (x.is_cuda and x.dtype == torch.bfloat16
+            and geglu_colsum_tiles(x.shape[-1]) and not using_eager_fallback(x))
 
 
 def geglu_bwd_colsum(x, dout):

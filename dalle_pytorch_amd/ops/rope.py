@@ -8,7 +8,8 @@ same way.
 
 import torch
 
-from dalle_pytorch_amd.ops.dispatch import hip_module
+from dalle_pytorch_amd.ops.dispatch import hip_module, using_eager_fallback
+
 
 def trig_tables(angles: torch.Tensor):
     """cos/sin fp32 [N, rot] for a rotary angle table [1, N, rot]; cached on
@@ -44,5 +45,5 @@ def rope_split(qkv, heads, cos=None, sin=None):
 
 
 def rope_split_supported(qkv, dim_head):
-    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and dim_head == 64
-            and hip_module() is not None)
+    return (qkv.dtype == torch.bfloat16 and dim_head == 64
+            and not using_eager_fallback(qkv))

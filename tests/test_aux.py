@@ -244,23 +244,78 @@ def test_bench_dump_outputs_cpu(tmp_path):
 
 
 def test_weight_caches_reject_recycled_storage():
-    """The per-step W^T / bf16-cast caches key on (data_ptr, shape). A new
-    parameter that lands on a freed one's address with the same shape and
-    version must not be served the old entry; the same parameter and fresh
-    slices of it must still hit."""
+    """The per-step weight caches (one class, three users: fp8 quant, bf16
+    cast, bf16 W^T) key on (data_ptr, shape). A new parameter that lands on
+    a freed one's address with the same shape and version must not be served
+    the old entry; the same parameter and fresh slices of it must still hit.
+    An entry lasts until the parameter's version or the step changes, and a
+    full cache empties itself."""
     from dalle_pytorch_amd.ops import fp8
+    users = (fp8._quant_weight, fp8._bf16_weight, fp8._transposed_weight)
+    assert all(type(u) is fp8._StepCache for u in users)
+    assert len({id(u.entries) for u in users}) == 3
+
+    made = []
+
+    def make(w):
+        made.append(w)
+        return w.detach().to(torch.bfloat16).t().contiguous()
+
+    cache = fp8._StepCache(make)
     p = torch.nn.Parameter(torch.randn(32, 16))
-    assert fp8._transposed_weight(p) is fp8._transposed_weight(p)
-    assert fp8._transposed_weight(p[:16]) is fp8._transposed_weight(p[:16])
-    assert fp8._cached_bf16(p) is fp8._cached_bf16(p)
+    assert cache(p) is cache(p)
+    assert cache(p[:16]) is cache(p[:16])
+    assert len(made) == 2
     # what address reuse produces: q's key maps to the entry p left behind
     q = torch.nn.Parameter(torch.randn(32, 16))
-    for cache in (fp8._wt_cache, fp8._cast_cache):
-        cache[(q.data_ptr(), tuple(q.shape))] = \
-            cache[(p.data_ptr(), tuple(p.shape))]
+    cache.entries[(q.data_ptr(), tuple(q.shape))] = \
+        cache.entries[(p.data_ptr(), tuple(p.shape))]
     qb = q.detach().to(torch.bfloat16)
-    assert torch.equal(fp8._transposed_weight(q), qb.t())
-    assert torch.equal(fp8._cached_bf16(q), qb)
+    assert torch.equal(cache(q), qb.t())
+    assert len(made) == 3 and cache(q) is cache(q)
+
+    # a version bump misses, and so does the step mark
+    hit = cache(p)
+    with torch.no_grad():
+        p.add_(1)
+    bumped = cache(p)
+    assert bumped is not hit
+    assert torch.equal(bumped, p.detach().to(torch.bfloat16).t())
+    fp8.fp8_mark_step()
+    assert cache(p) is not bumped and cache(p) is cache(p)
+
+    # the bound: 512 entries stay, the 513th insert clears the rest
+    cache = fp8._StepCache(lambda w: w.detach().clone())
+    params = [torch.nn.Parameter(torch.zeros(1)) for _ in range(513)]
+    for w in params[:512]:
+        cache(w)
+    assert len(cache.entries) == 512
+    cache(params[512])
+    assert len(cache.entries) == 1 and cache(params[512]) is cache(params[512])
+
+
+def test_gpu_tensor_without_extension_is_loud(monkeypatch):
+    """Dispatch policy: a GPU tensor with the extension missing raises from
+    every eligibility predicate instead of quietly choosing the eager route;
+    DALLE_AMD_ALLOW_EAGER=1 turns that into a plain 'not supported'."""
+    from types import SimpleNamespace
+    from dalle_pytorch_amd.ops import dispatch
+    from dalle_pytorch_amd.ops.fused import (layer_norm_fused,
+                                              token_shift_supported)
+    from dalle_pytorch_amd.ops.rope import rope_split_supported
+    monkeypatch.setattr(dispatch, '_TRIED', True)
+    monkeypatch.setattr(dispatch, '_HIP', None)
+    x = SimpleNamespace(is_cuda=True, dtype=torch.bfloat16, shape=(2, 8, 512),
+                        element_size=lambda: 2)
+    checks = (lambda: token_shift_supported(x),
+              lambda: rope_split_supported(x, 64),
+              lambda: layer_norm_fused(x))
+    monkeypatch.delenv('DALLE_AMD_ALLOW_EAGER', raising=False)
+    for check in checks:
+        with pytest.raises(RuntimeError, match='is not built'):
+            check()
+    monkeypatch.setenv('DALLE_AMD_ALLOW_EAGER', '1')
+    assert not any(check() for check in checks)
 
 
 def test_clip_train_and_rerank(tmp_path):
