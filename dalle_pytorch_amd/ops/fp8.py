@@ -8,8 +8,9 @@ weights stay bf16/fp32 — fp8 exists only on the wire into the GEMM:
   (the eager cast chain costs more than the fp8 GEMM saves);
 * weights: quantized once per optimizer step (cached on the parameter's
   version counter, so the reversible recompute pass reuses it);
-* backward: standard bf16 dgrad/wgrad — fp8 is forward-only, which under
-  reversible execution still covers 2 of the 4 GEMM passes per step.
+* backward: bf16 dgrad/wgrad (transposed-weight dgrad, split-K wgrad on the
+  long-reduction shapes) — fp8 is forward-only, which under reversible
+  execution still covers 2 of the 4 GEMM passes per step.
 
 Enable with DALLE_AMD_FP8=1 (or ``set_fp8_enabled(True)``; bench.py
 exposes ``--fp8``). Default OFF: the headline BASELINE numbers are bf16.
@@ -151,13 +152,84 @@ def _gemm_forward(x, weight, bias):
     return x2, out
 
 
+# Split-K weight gradient (ops/hip/wgrad.hip). dW = do2^T x2 has a small
+# output and a very long reduction: the flagship shapes give 16-128 macro-
+# tiles of 256 x 256 on 256 CUs, so a single GEMM leaves half the chip idle.
+# Constants from profiles/probe_wgrad.txt (scripts/probe_wgrad.py; 81920 rows
+# unless stated, fp32 output, "today" = bf16 GEMM + the cast to fp32):
+#   dW              today    best S        rule
+#   8192 x 1024    1252 us    2: 1204 us     2   ff1 (2-4% in every run)
+#   1024 x 4096     702 us    4:  627 us     4   ff2
+#   3072 x 1024     686 us    4:  474 us     4   qkv (S = 8: 493 us)
+#   1024 x 1024     419 us   16:  182 us    16   out-proj (S = 32: 195 us)
+#   10256 x 1024    525 us    2:  376 us     2   text CE head, 16448 rows
+#                                                (S = 4, 4112-row chunks: 462)
+# i.e. split until S x tiles reaches 192; a target of 256 would pick S = 8
+# for qkv. The fp32-output GEMM alone (S = 1) ties with today's GEMM + cast,
+# so a shape that is not split keeps today's expression.
+WGRAD_TILE = 256          # macro-tile edge the tile count is taken in
+WGRAD_TILE_TARGET = 192   # split until S x tiles reaches this many
+# rows: nothing under 16448 rows was probed (config B runs 10240); chunks of
+# 5120 rows still gained over the next-lower S, chunks of 4112 rows lost
+WGRAD_ROW_FLOOR = 16384   # fewer rows than this: never split
+WGRAD_CHUNK_FLOOR = 5120  # rows per chunk, at least
+WGRAD_MAX_SPLITS = 32     # the reduce kernel's widest instantiation
+
+
+def wgrad_splits(rows, n, k):
+    """How many row chunks the weight gradient dW[n, k] of ``rows`` rows is
+    split into: the smallest power of two S for which S x (macro-tiles of dW)
+    fills the chip, among those that divide ``rows`` and leave chunks of at
+    least WGRAD_CHUNK_FLOOR rows. 1 (no split) below WGRAD_ROW_FLOOR rows and
+    where n or k is no multiple of 16. Shapes only: a pure function."""
+    if rows < WGRAD_ROW_FLOOR or n <= 0 or k <= 0 or n % 16 or k % 16:
+        return 1
+    tiles = -(-n // WGRAD_TILE) * -(-k // WGRAD_TILE)
+    s = 1
+    while (s * tiles < WGRAD_TILE_TARGET and s < WGRAD_MAX_SPLITS
+           and rows % (2 * s) == 0 and rows // (2 * s) >= WGRAD_CHUNK_FLOOR):
+        s *= 2
+    return s
+
+
+def wgrad_plan(do2, x2, out_dtype):
+    """Splits for torch.ops.dalle_amd.wgrad_splitk on these operands, or 0
+    for the plain ``do2.t() @ x2``: off the kernel path (CPU, eager
+    fallback, non-bf16 or non-contiguous operands, a weight dtype the reduce
+    does not store), with DALLE_AMD_WGRAD_SPLITK=0, and where the rule does
+    not split."""
+    # the shape rule first: small layers leave here at the cost of a compare
+    s = wgrad_splits(do2.shape[0], do2.shape[-1], x2.shape[-1])
+    if s <= 1:
+        return 0
+    if not fusion_enabled('WGRAD_SPLITK') or using_eager_fallback(do2):
+        return 0
+    if not (do2.dtype == x2.dtype == torch.bfloat16 and do2.dim() == 2
+            and x2.dim() == 2 and do2.is_contiguous() and x2.is_contiguous()
+            and out_dtype in (torch.float32, torch.bfloat16)):
+        return 0
+    return s
+
+
+def _wgrad_op(do2, x2, splits, out_dtype):
+    # registered by the extension's shared object (dispatcher op, not a
+    # pybind export); wgrad_plan has loaded it
+    return torch.ops.dalle_amd.wgrad_splitk(do2, x2, splits, out_dtype)
+
+
 def _gemm_backward(do2, x2, weight, lead):
     """(dx [*lead, k], dW) from the output gradient do2 [rows, n]:
-    transposed-weight dgrad, standard wgrad."""
+    transposed-weight dgrad; split-K wgrad, stored once in the weight's
+    dtype, where ``wgrad_plan`` splits, else the standard wgrad."""
     wt = _transposed_weight(weight)
     dx = (do2 @ wt.t()).reshape(*lead, weight.shape[1])
-    dw = do2.t() @ x2.to(do2.dtype)
-    return dx, dw.to(weight.dtype)
+    x2 = x2.to(do2.dtype)
+    splits = wgrad_plan(do2, x2, weight.dtype)
+    if splits:
+        dw = _wgrad_op(do2, x2, splits, weight.dtype)
+    else:
+        dw = (do2.t() @ x2).to(weight.dtype)
+    return dx, dw
 
 
 def _bf16_bias(bias):

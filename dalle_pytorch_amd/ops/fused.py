@@ -129,8 +129,9 @@ def add_scaled(x, y, gamma):
 
 def fusion_enabled(name):
     """Off switches for the fused training-tail paths, for A/B runs and
-    tests: DALLE_AMD_LN_SHIFT, DALLE_AMD_REV_REPLAY, DALLE_AMD_FF1_BIAS
-    (each default '1'; '0' restores the unfused path)."""
+    tests: DALLE_AMD_LN_SHIFT, DALLE_AMD_REV_REPLAY, DALLE_AMD_FF1_BIAS,
+    and DALLE_AMD_WGRAD_SPLITK for the split-K weight gradient (each
+    default '1'; '0' restores the earlier path)."""
     return env_flag(name, True)
 
 

@@ -20,7 +20,8 @@ from pathlib import Path
 PKG_DIR = Path(__file__).resolve().parents[2]   # dalle_pytorch_amd/
 SRC_DIR = Path(__file__).resolve().parent
 SOURCES = [SRC_DIR / name for name in (
-    'attention.hip', 'decode.hip', 'train_ops.hip', 'module.hip')]
+    'attention.hip', 'decode.hip', 'train_ops.hip', 'wgrad.hip',
+    'module.hip')]
 OBJ_DIR = SRC_DIR / 'build'                     # ignored by git
 OUTPUT = PKG_DIR / '_hip.so'
 MAX_JOBS = 16

@@ -10,6 +10,8 @@
 //                  residual scale, reversible replay, fp8 quantize
 //   decode.hip     the single-token decode family (key-split attention +
 //                  ring-buffer shift, the sk2 decode GEMM, sampler)
+//   wgrad.hip      split-K weight gradient: chunk GEMMs through ATen + the
+//                  fixed-order fp32 reduce of the partials (a dispatcher op)
 //   module.hip     the Python module definition
 // Written for wave64 / 8-XCD MI355X per the CDNA4 HIP guide — NOT a port of
 // any CUDA kernel.
